@@ -2,6 +2,15 @@
 4096 envs per GPU (BASELINE.json metric), one process per GPU.
 
     python bench.py [--gpus N --steps K --warmup W --envs 4096 --precision 64]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, burns in, warms up, times the K steps and prints one JSON
+line.  --full adds the secondary measurements to that line, each in a run of
+its own after the headline one: the fp64 CPU baseline (cpu_baseline), the
+single-env rate (single_env) and the same workload with the reference's
+integrator (reference_integrator).  --dump-outputs DIR writes what the last
+timed step returned (obs, reward, done, info) as DIR/<name>.npy; with the same
+arguments the inputs, and so these arrays, are the same from run to run.
 
 N > 1: the driver launches N ranks with torch.distributed.run (RANK /
 LOCAL_RANK / WORLD_SIZE set).  Run directly with --gpus N > 1, bench.py starts
@@ -172,6 +181,30 @@ def _profile_record(name, key, build_id):
     return rec
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, outputs, rank=0):
+    """Write the last step's outputs (name -> (N, ...) tensor, one row per env)
+    as <dirname>/<name>.npy (rank r > 0: <name>_rank<r>.npy), float32 for fp32
+    data and float64 otherwise.  More than DUMP_MAX_BYTES in all: the same
+    seeded sample of env rows of every array, its indices in rows.npy."""
+    import numpy as np
+    arrs = {k: v.detach().cpu().numpy() for k, v in outputs.items()}
+    arrs = {k: v if v.dtype == np.float32 else v.astype(np.float64) for k, v in arrs.items()}
+    n = len(next(iter(arrs.values())))
+    row_bytes = sum(v.nbytes for v in arrs.values()) / max(n, 1) + 8
+    keep = int(DUMP_MAX_BYTES // row_bytes)
+    if keep < n:
+        rows = np.sort(np.random.Generator(np.random.PCG64(0)).choice(n, size=keep, replace=False))
+        arrs = {k: v[rows] for k, v in arrs.items()}
+        arrs['rows'] = rows.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    suffix = f'_rank{rank}' if rank else ''
+    for k, v in arrs.items():
+        np.save(os.path.join(dirname, f'{k}{suffix}.npy'), np.ascontiguousarray(v))
+
+
 def _spawn_ranks(a):
     """`bench.py --gpus N` run directly: start torch.distributed.run as a child
     (nothing in this process has touched a GPU) and return its exit status."""
@@ -199,11 +232,17 @@ def main():
     ap.add_argument('--rk-budget', type=int, default=0,
                     help='rk-merson only: attempts per env per launch (bioim_set_rk_budget); value counts the env '
                          'steps that finished')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline measurement also run the secondary ones: the CPU baseline, the '
+                         'single-env rate and the reference-integrator rate (each has a --no-... switch)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last step returned (obs, reward, done, info) '
+                         'as DIR/<name>.npy')
     ap.add_argument('--no-reference-integrator', action='store_true',
-                    help='skip the second measurement: the same workload with the reference integrator '
+                    help='--full: skip the second measurement: the same workload with the reference integrator '
                          '(RK-Merson 1e-3, budgeted launches), reported as "reference_integrator"')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-single-env', action='store_true', help='skip the single-env (envs.make) rate')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-single-env', action='store_true', help='--full: skip the single-env (envs.make) rate')
     ap.add_argument('--mixed', default=None,
                     help="mixed batch 'ID_A,ID_B' split 50/50 per GPU (BASELINE config C5), e.g. "
                          "MuscleLockedKneeImitation3D-v0,MusclePalsyImitation3D-v0")
@@ -217,6 +256,8 @@ def main():
     a = ap.parse_args()
     if a.rk_budget and (a.integrator != 'rk-merson' or a.mixed):
         ap.error('--rk-budget needs --integrator rk-merson and a single env id')
+    if not a.full:   # a plain run measures the headline figure only
+        a.no_cpu_baseline = a.no_single_env = a.no_reference_integrator = True
 
     if 'WORLD_SIZE' not in os.environ and a.gpus > 1:
         sys.exit(_spawn_ranks(a))
@@ -332,6 +373,11 @@ def main():
     else:
         steps_total = steps_local
     value = steps_total / t_max
+    if a.dump_outputs:   # nothing has stepped the env since the last timed step
+        outs = {'obs': env.obs, 'reward': env.reward, 'done': env.done, 'info': env.info}
+        if a.rk_budget:
+            outs['ready'] = env.ready
+        dump_outputs(a.dump_outputs, outs, rank)
     done_rate = (sum(h.reset_count() for h in handles) - resets0) / max(steps_counted, 1)
     if rank == 0:
         real_bytes = 8 if a.precision == 64 else 4

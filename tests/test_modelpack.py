@@ -10,7 +10,7 @@ import pytest
 from bioimitation import packdef as P
 from bioimitation.registry import load_pack
 
-REF_DATA = '/root/reference/bioimitation/imitation_envs/data'
+from refdata import ref_data  # noqa: F401  (fixture: the reference's .osim models, unpacked from tests/golden/)
 
 
 def test_pack_layout_matches_oracle(oracle_lib):
@@ -117,15 +117,14 @@ def test_spline_interpolates_knots_and_is_c2():
     assert abs(simm_spline_eval(x, y, b, c, d, 3.0) - (y[-1] + (3.0 - x[-1]) * b[-1])) < 1e-15
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason='reference data not present')
-def test_predictive_transform_known_answer():
+def test_predictive_transform_known_answer(ref_data):  # noqa: F811
     """construct_predictive_model (opensim_utils.py:204-222) restated on the
     parsed model must reproduce the contact/limit parameters the reference
     shipped already-transformed in 02905_PRE/scale/model_predictive.osim."""
     from bioimitation.osim import load_osim
     from bioimitation import transforms
-    shipped = load_osim(os.path.join(REF_DATA, '02905/02905_PRE/scale/model_predictive.osim'))
-    ours = transforms.construct_predictive_model(load_osim(os.path.join(REF_DATA, '02905/02905_PRE/scale/model_scaled.osim')))
+    shipped = load_osim(os.path.join(ref_data, '02905/02905_PRE/scale/model_predictive.osim'))
+    ours = transforms.construct_predictive_model(load_osim(os.path.join(ref_data, '02905/02905_PRE/scale/model_scaled.osim')))
     key = lambda s: (s.name, s.body, tuple(np.round(s.loc, 9)), round(s.radius, 9))
     assert sorted(map(key, ours.spheres)) == sorted(map(key, shipped.spheres))
     hk = lambda h: (h.name, tuple(h.geometries), h.stiffness, h.dissipation, h.static_friction,
@@ -137,14 +136,13 @@ def test_predictive_transform_known_answer():
     assert abs(ours.coords['pelvis_ty'].default_value - 1.02) < 1e-15
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason='reference data not present')
-def test_committed_packs_are_current():
+def test_committed_packs_are_current(ref_data):  # noqa: F811
     """The committed packs equal a fresh compile from the reference data."""
     from bioimitation import modelpack, refmotion, registry
     data = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'bioimitation-gym_amd',
                         'bioimitation', 'data')
     for env_id, rec in registry.RECIPES.items():
-        model = registry.build_model(env_id, REF_DATA)
+        model = registry.build_model(env_id, ref_data)
         ref = refmotion.load_reference_tables(os.path.join(data, rec['reference']), model.coord_order)
         fresh = modelpack.pack_bytes(modelpack.compile_pack(model, registry.env_spec(env_id), ref))
         committed = modelpack.pack_bytes(load_pack(env_id))

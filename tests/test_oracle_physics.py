@@ -10,9 +10,10 @@ import pytest
 
 from bioimitation.registry import load_pack
 
+from refdata import ref_data  # noqa: F401  (fixture: the reference's .osim models, unpacked from tests/golden/)
+
 ENVS = ['MuscleWalkingImitation2D-v0', 'MuscleRunningImitation3D-v0', 'MuscleLockedKneeImitation3D-v0',
         'MusclePalsyImitation3D-v0']
-REF_DATA = '/root/reference/bioimitation/imitation_envs/data'
 
 
 @pytest.fixture(scope='module', params=ENVS)
@@ -41,13 +42,11 @@ def random_q(pk, rng, scale=0.5):
     return q + rng.normal(0, scale, pk.ndof)
 
 
-def test_forward_kinematics_matches_raw_joint_chain(orc):
+def test_forward_kinematics_matches_raw_joint_chain(orc, ref_data):  # noqa: F811
     """Composite-body FK (compiled pack) == FK straight from the parsed joints."""
     from bioimitation import modelpack, registry
-    if not os.path.isdir(REF_DATA):
-        pytest.skip('reference data not present')
     pk = orc.pack
-    m = registry.build_model(pk.env_id.decode(), REF_DATA)
+    m = registry.build_model(pk.env_id.decode(), ref_data)
     rng = np.random.default_rng(0)
     for _ in range(5):
         q = random_q(pk, rng)

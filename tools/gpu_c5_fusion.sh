@@ -9,7 +9,7 @@ timeout -k 10 300 python -u -m pytest tests/test_gpu_parity.py -m gpu -x -v --ti
 for r in 1 2 3; do
   for F in "" "--no-fuse"; do
     tag=fused; [ -n "$F" ] && tag=concurrent
-    timeout -k 10 200 python bench.py --mixed MuscleLockedKneeImitation3D-v0,MusclePalsyImitation3D-v0 --no-cpu-baseline $F > $O/c5_${tag}_$r.json 2>> $O/bench.err
+    timeout -k 10 200 python bench.py --full --mixed MuscleLockedKneeImitation3D-v0,MusclePalsyImitation3D-v0 --no-cpu-baseline $F > $O/c5_${tag}_$r.json 2>> $O/bench.err
   done
 done
 python3 - $O <<'PY'

@@ -10,10 +10,10 @@ TAG=${1:-r01}
 O=gpurun_out/ev_${TAG}
 mkdir -p $O
 export TMPDIR=/tmp
-timeout -k 10 400 python bench.py > $O/bench_fp64.json 2> $O/bench.err
-timeout -k 10 200 python bench.py --precision 32 --no-cpu-baseline > $O/bench_fp32.json 2>> $O/bench.err
-timeout -k 10 200 python bench.py --env-id MuscleRunningImitation3D-v0 --no-cpu-baseline > $O/bench_3d_fp64.json 2>> $O/bench.err
-timeout -k 10 200 python bench.py --mixed MuscleLockedKneeImitation3D-v0,MusclePalsyImitation3D-v0 > $O/bench_mixed_fp64.json 2>> $O/bench.err
+timeout -k 10 400 python bench.py --full > $O/bench_fp64.json 2> $O/bench.err
+timeout -k 10 200 python bench.py --full --precision 32 --no-cpu-baseline > $O/bench_fp32.json 2>> $O/bench.err
+timeout -k 10 200 python bench.py --full --env-id MuscleRunningImitation3D-v0 --no-cpu-baseline > $O/bench_3d_fp64.json 2>> $O/bench.err
+timeout -k 10 200 python bench.py --full --mixed MuscleLockedKneeImitation3D-v0,MusclePalsyImitation3D-v0 > $O/bench_mixed_fp64.json 2>> $O/bench.err
 for CFG in "2d:--env-id MuscleWalkingImitation2D-v0" "3d:--env-id MuscleRunningImitation3D-v0"; do
     K=${CFG%%:*}; A="${CFG#*:} --steps 20 --warmup 3 --no-cpu-baseline"
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${K}_trace -o trace -- python3 bench.py $A > $O/${K}_trace.log 2>&1

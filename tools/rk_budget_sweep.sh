@@ -9,7 +9,7 @@ out=$1; shift; mkdir -p "$out"
 budgets=${@:-"2 3 4 5 6 8"}
 for id in MuscleWalkingImitation2D-v0 MuscleRunningImitation3D-v0 TorqueWalkingImitation2D-v0; do
   for b in $budgets; do
-    timeout -k 10 300 python bench.py --no-cpu-baseline --env-id $id --integrator rk-merson --rk-budget $b --steps 200 > "$out/bench_rk_b${b}_$id.json"
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline --env-id $id --integrator rk-merson --rk-budget $b --steps 200 > "$out/bench_rk_b${b}_$id.json"
   done
 done
 echo done
