@@ -325,17 +325,122 @@ class VectorEnv:
         _lib.check(self._L.bioim_get_state(self._h, s.ctypes.data_as(C.POINTER(C.c_double))))
         return s
 
-    def state_rows(self, out=None):
+    def _id_list(self, ids, what, distinct):
+        """Env ids for the indexed state calls -> (host int64 array, int32
+        device tensor or None).  Lists, ranges and numpy arrays are checked on
+        the host alone (no device synchronization; ``_upload_ids`` then takes
+        them to the device).  A device tensor goes through ``_env_ids`` (one
+        synchronizing copy back) and is returned as the second value.  Ids
+        lie in [0, num_envs) and, with ``distinct``, do not repeat."""
+        import torch
+        if isinstance(ids, torch.Tensor):
+            if ids.dtype in (torch.bool, torch.float16, torch.bfloat16, torch.float32, torch.float64):
+                raise ValueError(f'{what} ids must be integers, got {ids.dtype}')
+            if distinct:
+                dev = self._env_ids(ids)
+                return dev.cpu().numpy().astype(np.int64), dev
+            dev = torch.as_tensor(ids, dtype=torch.int32, device=self.device).reshape(-1).contiguous()
+            ids = dev.cpu().numpy()
+        else:
+            dev = None
+        host = np.asarray(ids).reshape(-1)
+        if host.size and host.dtype.kind not in 'iu':
+            raise ValueError(f'{what} ids must be integers, got {host.dtype}')
+        host = host.astype(np.int64)
+        if host.size and (host.min() < 0 or host.max() >= self.num_envs):
+            raise ValueError(f'{what} ids must lie in [0, {self.num_envs})')
+        if distinct and np.unique(host).size != host.size:
+            raise ValueError(f'{what} ids must be distinct')
+        return host, dev
+
+    def _upload_ids(self, host):
+        """host ids (any shape) as an int32 device tensor, copied from pinned
+        memory on the current stream without waiting for the device"""
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32)).pin_memory().to(self.device, non_blocking=True)
+
+    def _check_rows(self, t, n, what):
+        """a buffer the state kernels read or write n * state_dim doubles of"""
+        import torch
+        if not isinstance(t, torch.Tensor) or t.shape != (n, self.state_dim) or t.dtype != torch.float64 \
+                or t.device != self.device or not t.is_contiguous():
+            raise ValueError(f'{what} must be a contiguous ({n}, {self.state_dim}) torch.float64 tensor on {self.device}')
+
+    def state_rows(self, out=None, env_ids=None):
         """The flat state rows of get_state as a (N, state_dim) float64 device
         tensor, gathered on the env's stream without synchronizing
         (bioim_copy_state): one transfer can carry them with a step's
-        outputs."""
+        outputs.  ``env_ids``: the rows of the listed envs only, in the
+        list's order, as (len(env_ids), state_dim) (bioim_copy_state_rows).
+        ``out``: a contiguous float64 tensor of that shape on the env's
+        device to write them to."""
         import torch
+        ids = None
+        n = self.num_envs
+        if env_ids is not None:
+            host, ids = self._id_list(env_ids, 'env', distinct=False)
+            n = host.size
         if out is None:
-            out = torch.empty((self.num_envs, self.state_dim), dtype=torch.float64, device=self.device)
+            out = torch.empty((n, self.state_dim), dtype=torch.float64, device=self.device)
+        else:
+            self._check_rows(out, n, 'state_rows: out')
+        if n == 0:
+            return out
         self._bind_stream()
-        _lib.check(self._L.bioim_copy_state(self._h, self._ptr(out)))
+        if env_ids is not None and ids is None:
+            ids = self._upload_ids(host)
+        if ids is None:
+            _lib.check(self._L.bioim_copy_state(self._h, self._ptr(out)))
+        else:
+            _lib.check(self._L.bioim_copy_state_rows(self._h, self._ptr(ids), n, self._ptr(out)))
         return out
+
+    def load_state(self, rows, env_ids=None):
+        """Write flat state rows (``state_rows``' layout: a contiguous
+        (n, state_dim) float64 tensor on the env's device) into the listed
+        envs, row i into env ``env_ids[i]`` (default: all envs in order), on
+        the env's stream without synchronizing (bioim_load_state).  As with
+        ``set_state`` the written envs are at a step boundary and their
+        realize cache is stale; unlike it, every other env — its realize
+        cache included — is left alone."""
+        self._bind_stream()
+        ids = None
+        n = self.num_envs
+        if env_ids is not None:
+            host, ids = self._id_list(env_ids, 'env', distinct=True)
+            n = host.size
+        self._check_rows(rows, n, 'load_state: rows')
+        if n == 0:
+            return
+        if env_ids is not None and ids is None:
+            ids = self._upload_ids(host)
+        _lib.check(self._L.bioim_load_state(self._h, self._ptr(ids), n, self._ptr(rows)))
+
+    def clone_envs(self, src, dst):
+        """Make every env of ``dst`` an exact copy of its ``src`` env (an int:
+        one source for all; or one id per dst), in one launch on the env's
+        stream (bioim_clone_envs).  The whole per-env record travels — also
+        what the flat state row lacks: the fiber-velocity warm starts, the
+        realize-cache row and a suspended RK step — so a clone continues bit
+        for bit like its source under the same actions.  Reset and RK
+        counters stay with their envs.  ``dst`` ids are distinct and none is
+        also a source."""
+        self._bind_stream()
+        dst_h, dst_d = self._id_list(dst, 'dst', distinct=True)
+        n = dst_h.size
+        if isinstance(src, (int, np.integer)):
+            src = np.full(n, int(src), dtype=np.int64)
+        src_h, src_d = self._id_list(src, 'src', distinct=False)
+        if src_h.size != n:
+            raise ValueError(f'clone_envs: {src_h.size} src ids for {n} dst ids')
+        if np.intersect1d(src_h, dst_h).size:
+            raise ValueError('clone_envs: an env cannot be both a src and a dst')
+        if n == 0:
+            return
+        if src_d is None or dst_d is None:     # one upload for both lists
+            both = self._upload_ids(np.stack([src_h, dst_h]))
+            src_d, dst_d = both[0], both[1]
+        _lib.check(self._L.bioim_clone_envs(self._h, self._ptr(src_d), self._ptr(dst_d), n))
 
     def set_state(self, s: np.ndarray):
         s = np.ascontiguousarray(s, dtype=np.float64)

@@ -4486,6 +4486,7 @@ BIOIM_FOR_EACH_TOPOLOGY(BIOIM_PICK_DEF)
 
 #if !defined(BIOIM_TOPO_ONLY) && !defined(BIOIM_FUSED_ONLY)
 thread_local std::string g_err;
+static bool state_planes_match(const bioim_handle_t *h);   /* with the plane table, next to bioim_copy_state */
 
 /* ================================================================ C-ABI */
 extern "C" {
@@ -4542,6 +4543,10 @@ int bioim_create(const bioim_modelpack_t *pack, int n_envs, int device, int prec
     }
     int rc = precision == 64 ? alloc_state<double>(h) : alloc_state<float>(h);
     if (rc) { bioim_destroy(h); return rc; }
+    if (!state_planes_match(h)) {   /* bioim_clone_envs would miss or misplace a plane */
+        bioim_destroy(h);
+        return fail(BIOIM_E_LAUNCH, "bioim_create: the state plane table does not reproduce state_layout");
+    }
     *out = h;
     return 0;
 }
@@ -4935,44 +4940,272 @@ int bioim_get_state(bioim_handle_t *h, double *host_state) {
 /* bioim_copy_state: the flat state rows (bioim_get_state's layout) gathered
  * on the device, one thread per value, on the handle's stream — no
  * synchronization, so a caller can fold them into the copy of a step's
- * outputs (the single-env recorder, envs.py) */
+ * outputs (the single-env recorder, envs.py).  bioim_copy_state_rows does
+ * the same for a list of envs, bioim_load_state writes such rows back and
+ * bioim_clone_envs copies whole envs.
+ *
+ * The kernels below (rows gather, rows load, env clone) take
+ * the model's sizes as run-time arguments: no topology template, this unit
+ * alone holds them.  Each reads its env ids from a device list and skips an
+ * id outside [0, N) instead of using it.
+ *
+ * state_rows_kernel: row r of out = the flat state row of env ids[r] (ids
+ * null: env r), n rows.  state_load_kernel: the inverse, with xfer_state's
+ * conversions; the thread of a row's first value also marks the env as at a
+ * step boundary (pend) and its realize-cache row as stale (cache_ok). */
 extern "C++" {
 template <typename Real>
-__global__ void state_rows_kernel(DState<Real> st, int n, int nd, int nm, int na, int H, int dim, double *out) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)n * dim) return;
-    const int e = (int)(i / dim);
+__global__ void state_rows_kernel(DState<Real> st, int n_envs, const int32_t *ids, int n, int nd, int nm, int na, int H,
+                                  int dim, double *out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, total = (size_t)n * dim;
+    if (i >= total) return;
+    const int r = (int)(i / dim);
     int k = (int)(i % dim);
-    const size_t N = (size_t)n;
+    const int e = ids ? GAT(ids, r, n) : r;
+    if (e < 0 || e >= n_envs) return;
+    const size_t N = (size_t)n_envs;
     double v = 0;
     if (k < 5) {
-        v = k == 0 ? st.t[e] : k == 1 ? (double)st.istep[e] : k == 2 ? (double)st.has_last[e]
-          : k == 3 ? (double)st.old_px[e] : (double)st.done[e];
-    } else if ((k -= 5) < nd) v = st.q[k * N + e];
-    else if ((k -= nd) < nd) v = st.u[k * N + e];
-    else if ((k -= nd) < nm) v = st.act[k * N + e];
-    else if ((k -= nm) < nm) v = st.lce[k * N + e];
-    else if ((k -= nm) < H * na) v = st.hist[k * N + e];   /* [hh][a] = hh * na + a */
-    else if ((k -= H * na) < na) v = st.last[k * N + e];
-    else if ((k -= na) == 0) v = st.hrk[e];
-    else v = st.ctl[(k - 1) * N + e];
-    out[i] = v;
+        v = k == 0 ? GAT(st.t, e, N) : k == 1 ? (double)GAT(st.istep, e, N) : k == 2 ? (double)GAT(st.has_last, e, N)
+          : k == 3 ? (double)GAT(st.old_px, e, N) : (double)GAT(st.done, e, N);
+    } else if ((k -= 5) < nd) v = GAT(st.q, k * N + e, nd * N);
+    else if ((k -= nd) < nd) v = GAT(st.u, k * N + e, nd * N);
+    else if ((k -= nd) < nm) v = GAT(st.act, k * N + e, nm * N);
+    else if ((k -= nm) < nm) v = GAT(st.lce, k * N + e, nm * N);
+    else if ((k -= nm) < H * na) v = GAT(st.hist, k * N + e, (size_t)H * na * N);   /* [hh][a] = hh * na + a */
+    else if ((k -= H * na) < na) v = GAT(st.last, k * N + e, na * N);
+    else if ((k -= na) == 0) v = GAT(st.hrk, e, N);
+    else v = GAT(st.ctl, (k - 1) * N + e, na * N);
+    GAT(out, i, total) = v;
+}
+
+template <typename Real>
+__global__ void state_load_kernel(DState<Real> st, int n_envs, const int32_t *ids, int n, int nd, int nm, int na, int H,
+                                  int dim, const double *rows) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, total = (size_t)n * dim;
+    if (i >= total) return;
+    const int r = (int)(i / dim);
+    int k = (int)(i % dim);
+    const int e = ids ? GAT(ids, r, n) : r;
+    if (e < 0 || e >= n_envs) return;
+    const size_t N = (size_t)n_envs;
+    const double v = GAT(rows, i, total);
+    if (k == 0) {
+        GAT(st.t, e, N) = v;
+        GAT(st.pend, e, N) = 0;       /* a state set from outside is at a step boundary */
+        GAT(st.cache_ok, e, N) = 0;   /* the realize cache belongs to the state it was formed at */
+    } else if (k == 1) GAT(st.istep, e, N) = (int32_t)v;
+    else if (k == 2) GAT(st.has_last, e, N) = (int32_t)v;
+    else if (k == 3) GAT(st.old_px, e, N) = (Real)v;
+    else if (k == 4) GAT(st.done, e, N) = (int32_t)v;
+    else if ((k -= 5) < nd) GAT(st.q, k * N + e, nd * N) = (Real)v;
+    else if ((k -= nd) < nd) GAT(st.u, k * N + e, nd * N) = (Real)v;
+    else if ((k -= nd) < nm) GAT(st.act, k * N + e, nm * N) = (Real)v;
+    else if ((k -= nm) < nm) GAT(st.lce, k * N + e, nm * N) = (Real)v;
+    else if ((k -= nm) < H * na) GAT(st.hist, k * N + e, (size_t)H * na * N) = (Real)v;
+    else if ((k -= H * na) < na) GAT(st.last, k * N + e, na * N) = (Real)v;
+    else if ((k -= na) == 0) GAT(st.hrk, e, N) = v;
+    else GAT(st.ctl, (k - 1) * N + e, na * N) = (Real)v;
+}
+
+/* The per-env record: every plane of DState, in state_layout's order.  The
+ * clone launch walks this table, and bioim_create checks it against the
+ * pointers state_layout produced (state_planes_match), so a plane added to
+ * the state cannot be left out of it silently. */
+enum PlaneElem { PE_REAL, PE_F64, PE_I32, PE_U64 };
+enum PlaneCount { PC_ONE, PC_NDOF, PC_NM1, PC_HIST, PC_NACT, PC_NA1, PC_CACHE };   /* elements per env */
+enum PlaneLayout { PL_SOA, PL_ROWS };   /* [count][N], env fastest | [N][count], row-major per env */
+struct StatePlane {
+    const char *name;
+    size_t member;   /* offset of the plane's pointer in DState (the same for both precisions) */
+    PlaneElem elem;
+    PlaneCount count;
+    PlaneLayout layout;
+    bool cloned;
+};
+#define BIOIM_PLANE(m, elem, count, layout, cloned) {#m, __builtin_offsetof(DState<double>, m), elem, count, layout, cloned}
+static const StatePlane g_state_planes[] = {
+    BIOIM_PLANE(q, PE_REAL, PC_NDOF, PL_SOA, true),
+    BIOIM_PLANE(u, PE_REAL, PC_NDOF, PL_SOA, true),
+    BIOIM_PLANE(act, PE_REAL, PC_NM1, PL_SOA, true),
+    BIOIM_PLANE(lce, PE_REAL, PC_NM1, PL_SOA, true),
+    BIOIM_PLANE(hist, PE_REAL, PC_HIST, PL_SOA, true),
+    BIOIM_PLANE(last, PE_REAL, PC_NACT, PL_SOA, true),
+    BIOIM_PLANE(old_px, PE_REAL, PC_ONE, PL_SOA, true),
+    BIOIM_PLANE(t, PE_F64, PC_ONE, PL_SOA, true),
+    BIOIM_PLANE(istep, PE_I32, PC_ONE, PL_SOA, true),
+    BIOIM_PLANE(has_last, PE_I32, PC_ONE, PL_SOA, true),
+    BIOIM_PLANE(done, PE_I32, PC_ONE, PL_SOA, true),
+    BIOIM_PLANE(resets, PE_I32, PC_ONE, PL_SOA, false),   /* the env's share of bioim_reset_count */
+    BIOIM_PLANE(hrk, PE_F64, PC_ONE, PL_SOA, true),
+    BIOIM_PLANE(pend, PE_I32, PC_ONE, PL_SOA, true),
+    BIOIM_PLANE(rkt, PE_F64, PC_ONE, PL_SOA, true),
+    BIOIM_PLANE(rkh, PE_F64, PC_ONE, PL_SOA, true),
+    BIOIM_PLANE(rka, PE_I32, PC_ONE, PL_SOA, true),
+    BIOIM_PLANE(ctl, PE_REAL, PC_NA1, PL_SOA, true),
+    BIOIM_PLANE(cur, PE_REAL, PC_NA1, PL_SOA, true),
+    BIOIM_PLANE(vnw, PE_REAL, PC_NM1, PL_SOA, true),
+    BIOIM_PLANE(rkev, PE_U64, PC_ONE, PL_SOA, false),     /* its share of bioim_eval_count / bioim_finished_count */
+    BIOIM_PLANE(cache, PE_REAL, PC_CACHE, PL_ROWS, true),
+    BIOIM_PLANE(cache_ok, PE_I32, PC_ONE, PL_SOA, true),
+};
+#undef BIOIM_PLANE
+constexpr int BIOIM_NPLANES = (int)(sizeof(g_state_planes) / sizeof(g_state_planes[0]));
+static_assert(sizeof(DState<double>) == BIOIM_NPLANES * sizeof(void *) && sizeof(DState<float>) == sizeof(DState<double>),
+              "g_state_planes must list every plane of DState");
+
+static size_t plane_count(const bioim_handle_t *h, PlaneCount c) {
+    switch (c) {
+    case PC_NDOF: return (size_t)h->ndof;
+    case PC_NM1: return h->nmuscle ? (size_t)h->nmuscle : 1;
+    case PC_HIST: return (size_t)BIOIM_MAX_HORIZON * h->nact;
+    case PC_NACT: return (size_t)h->nact;
+    case PC_NA1: return h->nact ? (size_t)h->nact : 1;
+    case PC_CACHE: return (size_t)cache_dim(h);
+    default: return 1;
+    }
+}
+static size_t plane_elem_bytes(const bioim_handle_t *h, PlaneElem e) {
+    return e == PE_I32 ? 4 : e == PE_REAL ? (h->precision == 64 ? 8 : 4) : 8;
+}
+static char *plane_base(const bioim_handle_t *h, const StatePlane &p) {
+    return *reinterpret_cast<char *const *>(reinterpret_cast<const char *>(h->dstate) + p.member);
+}
+/* the table reproduces state_layout: same order, sizes and 256-byte rounding */
+static bool state_planes_match(const bioim_handle_t *h) {
+    size_t off = 0;
+    for (const StatePlane &p : g_state_planes) {
+        if (plane_base(h, p) != (char *)h->state_buf + off) return false;
+        off += (plane_elem_bytes(h, p.elem) * plane_count(h, p.count) * (size_t)h->n + 255) & ~(size_t)255;
+    }
+    return off == h->state_bytes;
+}
+
+/* clone_envs_kernel's view of the cloned planes.  SoA planes are copied as
+ * 4- or 8-byte words (bit copies, whatever the element type); end[k] is the
+ * running sum of their rows per env, so a thread's row index names its plane. */
+struct ClonePlanes {
+    void *base[BIOIM_NPLANES];
+    int32_t end[BIOIM_NPLANES];
+    int32_t wide[BIOIM_NPLANES];   /* 1: 8-byte elements */
+    int32_t npl, rows;             /* SoA planes; their rows per env in all */
+    void *cache;                   /* the one [N][cache_dim] plane */
+    int32_t cache_dim, cache_wide;
+};
+
+template <typename W> DEV void clone_word(void *base, size_t to, size_t from, size_t count) {
+    W *b = reinterpret_cast<W *>(base);
+    GAT(b, to, count) = GAT(b, from, count);
+}
+
+/* Pair p copies env src[p]'s record to env dst[p].  The first n * rows
+ * threads take the SoA planes with the pair index fastest (a sorted dst
+ * writes coalesced), the others the cache rows with the element fastest. */
+__global__ void clone_envs_kernel(ClonePlanes pl, int n_envs, const int32_t *src, const int32_t *dst, int n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t N = (size_t)n_envs, nsoa = (size_t)n * pl.rows, total = nsoa + (size_t)n * pl.cache_dim;
+    if (i >= total) return;
+    const bool soa = i < nsoa;
+    const size_t j = soa ? i : i - nsoa;
+    const int p = soa ? (int)(j % n) : (int)(j / pl.cache_dim);
+    const int s = GAT(src, p, n), d = GAT(dst, p, n);
+    if (s < 0 || s >= n_envs || d < 0 || d >= n_envs) return;
+    if (!soa) {
+        const size_t c = j % pl.cache_dim, cd = (size_t)pl.cache_dim;
+        if (pl.cache_wide) clone_word<uint64_t>(pl.cache, d * cd + c, s * cd + c, N * cd);
+        else clone_word<uint32_t>(pl.cache, d * cd + c, s * cd + c, N * cd);
+        return;
+    }
+    const int row = (int)(j / n);
+    int first = 0;
+#pragma unroll
+    for (int k = 0; k < BIOIM_NPLANES; ++k) {
+        if (k < pl.npl && row >= first && row < pl.end[k]) {
+            const size_t r = (size_t)(row - first), count = (size_t)(pl.end[k] - first) * N;
+            if (pl.wide[k]) clone_word<uint64_t>(pl.base[k], r * N + d, r * N + s, count);
+            else clone_word<uint32_t>(pl.base[k], r * N + d, r * N + s, count);
+        }
+        first = pl.end[k];
+    }
 }
 }  // extern "C++"
 
-int bioim_copy_state(bioim_handle_t *h, void *device_out) {
-    if (!h || !device_out) return fail(BIOIM_E_ARG, "bioim_copy_state: bad arguments");
+static int state_rows_launch(bioim_handle_t *h, const int32_t *env_ids, int n, const double *rows_in, double *rows_out) {
     HIPCHK(hipSetDevice(h->device));
-    const int dim = bioim_state_dim(h), n = h->n;
+    const int dim = bioim_state_dim(h);
     const size_t total = (size_t)n * dim;
     const int bs = 256;
     const dim3 g((unsigned)((total + bs - 1) / bs)), b(bs);
-    if (h->precision == 64)
-        hipLaunchKernelGGL(state_rows_kernel<double>, g, b, 0, h->stream, *reinterpret_cast<DState<double> *>(h->dstate), n,
-                           h->ndof, h->nmuscle, h->nact, h->horizon, dim, reinterpret_cast<double *>(device_out));
-    else
-        hipLaunchKernelGGL(state_rows_kernel<float>, g, b, 0, h->stream, *reinterpret_cast<DState<float> *>(h->dstate), n,
-                           h->ndof, h->nmuscle, h->nact, h->horizon, dim, reinterpret_cast<double *>(device_out));
+    if (h->precision == 64) {
+        const DState<double> &st = *reinterpret_cast<DState<double> *>(h->dstate);
+        if (rows_out)
+            hipLaunchKernelGGL(state_rows_kernel<double>, g, b, 0, h->stream, st, h->n, env_ids, n, h->ndof, h->nmuscle,
+                               h->nact, h->horizon, dim, rows_out);
+        else
+            hipLaunchKernelGGL(state_load_kernel<double>, g, b, 0, h->stream, st, h->n, env_ids, n, h->ndof, h->nmuscle,
+                               h->nact, h->horizon, dim, rows_in);
+    } else {
+        const DState<float> &st = *reinterpret_cast<DState<float> *>(h->dstate);
+        if (rows_out)
+            hipLaunchKernelGGL(state_rows_kernel<float>, g, b, 0, h->stream, st, h->n, env_ids, n, h->ndof, h->nmuscle,
+                               h->nact, h->horizon, dim, rows_out);
+        else
+            hipLaunchKernelGGL(state_load_kernel<float>, g, b, 0, h->stream, st, h->n, env_ids, n, h->ndof, h->nmuscle,
+                               h->nact, h->horizon, dim, rows_in);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int bioim_copy_state(bioim_handle_t *h, void *device_out) {
+    if (!h || !device_out) return fail(BIOIM_E_ARG, "bioim_copy_state: bad arguments");
+    return state_rows_launch(h, nullptr, h->n, nullptr, reinterpret_cast<double *>(device_out));
+}
+
+int bioim_copy_state_rows(bioim_handle_t *h, const int32_t *env_ids, int n, void *device_out) {
+    if (!h) return fail(BIOIM_E_ARG, "bioim_copy_state_rows: null handle");
+    if (!device_out) return fail(BIOIM_E_ARG, "bioim_copy_state_rows: null output buffer");
+    if (env_ids && (n <= 0 || n > h->n))
+        return fail(BIOIM_E_ARG, "bioim_copy_state_rows: n must lie in [1, n_envs] with an id list");
+    return state_rows_launch(h, env_ids, env_ids ? n : h->n, nullptr, reinterpret_cast<double *>(device_out));
+}
+
+int bioim_load_state(bioim_handle_t *h, const int32_t *env_ids, int n, const void *device_rows) {
+    if (!h) return fail(BIOIM_E_ARG, "bioim_load_state: null handle");
+    if (!device_rows) return fail(BIOIM_E_ARG, "bioim_load_state: null rows buffer");
+    if (env_ids && (n <= 0 || n > h->n))
+        return fail(BIOIM_E_ARG, "bioim_load_state: n must lie in [1, n_envs] with an id list");
+    return state_rows_launch(h, env_ids, env_ids ? n : h->n, reinterpret_cast<const double *>(device_rows), nullptr);
+}
+
+int bioim_clone_envs(bioim_handle_t *h, const int32_t *src_ids, const int32_t *dst_ids, int n) {
+    if (!h) return fail(BIOIM_E_ARG, "bioim_clone_envs: null handle");
+    if (!src_ids || !dst_ids) return fail(BIOIM_E_ARG, "bioim_clone_envs: null src or dst id list");
+    if (n <= 0 || n > h->n) return fail(BIOIM_E_ARG, "bioim_clone_envs: n must lie in [1, n_envs]");
+    HIPCHK(hipSetDevice(h->device));
+    ClonePlanes pl{};
+    int rows = 0;
+    for (const StatePlane &p : g_state_planes) {
+        if (!p.cloned) continue;
+        const bool wide = plane_elem_bytes(h, p.elem) == 8;
+        if (p.layout == PL_ROWS) {
+            pl.cache = plane_base(h, p);
+            pl.cache_dim = (int32_t)plane_count(h, p.count);
+            pl.cache_wide = wide;
+            continue;
+        }
+        rows += (int)plane_count(h, p.count);
+        pl.base[pl.npl] = plane_base(h, p);
+        pl.end[pl.npl] = rows;
+        pl.wide[pl.npl] = wide;
+        ++pl.npl;
+    }
+    for (int k = pl.npl; k < BIOIM_NPLANES; ++k) pl.end[k] = rows;
+    pl.rows = rows;
+    const size_t total = (size_t)n * ((size_t)rows + pl.cache_dim);
+    const int bs = 256;
+    hipLaunchKernelGGL(clone_envs_kernel, dim3((unsigned)((total + bs - 1) / bs)), dim3(bs), 0, h->stream, pl, h->n,
+                       src_ids, dst_ids, n);
     HIPCHK(hipGetLastError());
     return 0;
 }

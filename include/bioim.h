@@ -213,6 +213,49 @@ int bioim_set_state(bioim_handle_t *h, const double *host_state);
  * boundary (bioim_get_state refuses them; this call does not check).  No
  * reference counterpart. */
 int bioim_copy_state(bioim_handle_t *h, void *device_out);
+/* Indexed state save / restore and env cloning on the device.  All three
+ * are asynchronous on the handle's stream and synchronize nothing; every
+ * pointer is a device pointer on the handle's device.  Argument errors (a
+ * null handle, a null buffer or id list, n <= 0 or n > N with an id list)
+ * return BIOIM_E_ARG with a message before any device call.  An id outside
+ * [0, N) is skipped by the kernels, never used.  No reference counterpart
+ * (the reference state is not checkpointable, and one OsimModel is one env).
+ *
+ * bioim_copy_state_rows: bioim_copy_state for the n listed envs — row i of
+ * device_out [n][state_dim] (doubles) is the flat state row of env
+ * env_ids[i]; ids may repeat.  env_ids NULL = all envs in order (n ignored).
+ * Like bioim_copy_state it does not check for envs suspended mid-step. */
+int bioim_copy_state_rows(bioim_handle_t *h, const int32_t *env_ids, int n, void *device_out);
+/* bioim_load_state: bioim_set_state for the n listed envs from device rows
+ * [n][state_dim] (doubles, bioim_get_state's layout) — row i goes to env
+ * env_ids[i] (distinct ids; NULL = all envs in order, n ignored), with
+ * bioim_set_state's conversions (values to the handle's precision; istep,
+ * has_last and done truncated to int32).  The listed envs are put at a step
+ * boundary (a suspended RK step is dropped) and their realize-cache rows are
+ * marked stale; their fiber-velocity warm starts and counters stay, as with
+ * bioim_set_state.  Every other env is left exactly as it is, its realize
+ * cache included (bioim_set_state clears every env's). */
+int bioim_load_state(bioim_handle_t *h, const int32_t *env_ids, int n, const void *device_rows);
+/* bioim_clone_envs: for each of the n pairs, env dst_ids[i] becomes a copy
+ * of env src_ids[i] that continues bit for bit like it under the same
+ * actions.  The whole per-env record is copied, not only the flat row:
+ * q, u, activations, fiber lengths, the action history, last action, old
+ * pelvis x, time, step index, has_last, done, the RK step size, the
+ * suspended-step record (pending flag, integration time, step size, attempt
+ * count, held controls, smoothed actions), the fiber-velocity warm starts
+ * and the realize-cache row with its valid flag.  A clone of an env that is
+ * suspended mid-step by the RK budget is suspended as well and resumes
+ * identically.  Not copied: the env's reset counter and RK counters (its
+ * shares of bioim_reset_count / bioim_eval_count / bioim_finished_count,
+ * which a clone therefore leaves unchanged) and its row of the push table
+ * (bioim_set_perturbation).  Device-drawn reset rows are a function of the
+ * seed, the global env index and the env's reset counter, so after its next
+ * reset without a ref_index (an auto-reset included) a clone draws its own
+ * row, not the one its source draws: the two part ways there.  The same src
+ * may appear many times; dst ids must be distinct and none of them may also
+ * be a src (the caller's contract: a violation races on that env's record,
+ * it does not leave the state buffer).  One launch. */
+int bioim_clone_envs(bioim_handle_t *h, const int32_t *src_ids, const int32_t *dst_ids, int n);
 
 /* Integrator of the physics between env steps.  kind 0: the fixed
  * semi-implicit substeps (the pack's nsub; default).  kind 1: the reference's
