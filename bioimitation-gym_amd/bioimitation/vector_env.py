@@ -447,6 +447,40 @@ class VectorEnv:
         assert s.shape == (self.num_envs, self.state_dim)
         _lib.check(self._L.bioim_set_state(self._h, s.ctypes.data_as(C.POINTER(C.c_double))))
 
+    def debug_plane(self, name, data=None):
+        """Debug / tests (``bioim_debug_plane``): one whole plane of the
+        per-env record (a ``DState`` member, by name) as a numpy array —
+        ``(count, N)`` with the env index fastest, ``(N, cache_dim)`` for the
+        realize cache, in the env's precision for the real-valued planes.
+        ``data``: write that array into the plane instead.  Synchronizes the
+        env's streams.  The library refuses a size that is not the plane's."""
+        pk, n = self.pack, self.num_envs
+        real = np.float32 if self.precision == 32 else np.float64
+        nd, nm1, na, na1 = pk.ndof, max(pk.nmuscle, 1), pk.nact, max(pk.nact, 1)
+        from .packdef import MAX_HORIZON
+        shapes = {'q': (real, nd), 'u': (real, nd), 'act': (real, nm1), 'lce': (real, nm1),
+                  'hist': (real, MAX_HORIZON * na), 'last': (real, na), 'old_px': (real, 1), 't': (np.float64, 1),
+                  'istep': (np.int32, 1), 'has_last': (np.int32, 1), 'done': (np.int32, 1), 'resets': (np.int32, 1),
+                  'hrk': (np.float64, 1), 'pend': (np.int32, 1), 'rkt': (np.float64, 1), 'rkh': (np.float64, 1),
+                  'rka': (np.int32, 1), 'ctl': (real, na1), 'cur': (real, na1), 'vnw': (real, nm1),
+                  'rkev': (np.uint64, 1)}
+        if name == 'cache':     # CacheLay: packed lower system, right-hand side, 3 per muscle, h
+            dtype, shape = real, (n, nd * (nd + 1) // 2 + nd + 3 * pk.nmuscle + 1)
+        elif name == 'cache_ok':
+            dtype, shape = np.int32, (1, n)
+        elif name in shapes:
+            dtype, shape = shapes[name][0], (shapes[name][1], n)
+        else:
+            raise ValueError(f'no state plane named {name!r}')
+        if data is None:
+            out = np.zeros(shape, dtype=dtype)
+            _lib.check(self._L.bioim_debug_plane(self._h, name.encode(), out.ctypes.data_as(C.c_void_p), out.nbytes, 0))
+            return out
+        arr = np.ascontiguousarray(data, dtype=dtype)
+        if arr.shape != shape:
+            raise ValueError(f'plane {name} has shape {shape}, got {arr.shape}')
+        _lib.check(self._L.bioim_debug_plane(self._h, name.encode(), arr.ctypes.data_as(C.c_void_p), arr.nbytes, 1))
+
     def reset_count(self) -> int:
         """Resets so far over all envs (explicit + in-kernel auto-resets)."""
         n = C.c_uint64()

@@ -4227,10 +4227,15 @@ void launch_impl(bioim_handle_t *h, int mode, const void *actions, void *obs, vo
     /* the realize cache (CacheLay): only the default step kernels form and
      * read it; before any other kernel changes the state, every env's row is
      * marked stale (once per switch: cache_live says a default launch may
-     * have set flags since) */
+     * have set flags since).  An OsimModel realize reads the state and moves
+     * none of it (the REP kernels store q/u/act/lce/t/istep back as loaded;
+     * with controls it writes ctl, which the stored system excludes and the
+     * next step's actuate replaces): the rows stay valid across it, so a
+     * read-only query leaves the next step's bits alone */
     const bool default_kernel = mode != 2 && a.pert_n == 0 && !h->rk;
+    const bool reads_only = mode == 2 && oc && oc->op == BIOIM_OSIM_REALIZE;
     if constexpr (CacheLay<T>::ON) {
-        if (!default_kernel && h->cache_live) {
+        if (!default_kernel && !reads_only && h->cache_live) {
             hipMemsetAsync(a.st.cache_ok, 0, sizeof(int32_t) * (size_t)h->n, h->stream);
             h->cache_live = 0;
         }
@@ -5279,6 +5284,35 @@ int bioim_set_rk_counters(bioim_handle_t *h, uint32_t evals, uint32_t finished) 
         for (int e = 0; e < h->n; ++e) hs.rkev[e] = v;
     }
     HIPCHK(hipMemcpy(h->state_buf, buf.data(), h->state_bytes, hipMemcpyHostToDevice));
+    return 0;
+}
+
+/* debug / tests: one whole plane of the per-env record (g_state_planes, by
+ * name) copied to the host, or from it.  Every argument check comes before
+ * the first device call. */
+int bioim_debug_plane(bioim_handle_t *h, const char *name, void *host, size_t bytes, int write) {
+    if (!h) return fail(BIOIM_E_ARG, "bioim_debug_plane: null handle");
+    if (!name || !host) return fail(BIOIM_E_ARG, "bioim_debug_plane: null plane name or host buffer");
+    const StatePlane *pl = nullptr;
+    for (const StatePlane &p : g_state_planes)
+        if (strcmp(p.name, name) == 0) pl = &p;
+    if (!pl) return fail(BIOIM_E_ARG, std::string("bioim_debug_plane: no plane named '") + name + "'");
+    const size_t want = plane_elem_bytes(h, pl->elem) * plane_count(h, pl->count) * (size_t)h->n;
+    if (bytes != want)
+        return fail(BIOIM_E_ARG, std::string("bioim_debug_plane: plane ") + name + " holds " + std::to_string(want) +
+                                     " bytes, the buffer " + std::to_string(bytes));
+    if (want == 0) return 0;   /* the cache plane of a topology without a realize cache */
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipStreamSynchronize(h->side));
+    if (write) {
+        HIPCHK(hipMemcpy(plane_base(h, *pl), host, want, hipMemcpyHostToDevice));
+        /* flags set from outside count as live: the next push, RK or
+         * OsimModel launch clears them like a default launch's (launch_impl) */
+        if (strcmp(name, "cache_ok") == 0) h->cache_live = 1;
+    } else {
+        HIPCHK(hipMemcpy(host, plane_base(h, *pl), want, hipMemcpyDeviceToHost));
+    }
     return 0;
 }
 

@@ -47,6 +47,7 @@
 #ifndef BIOIM_H
 #define BIOIM_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "bioim_modelpack.h"
@@ -188,7 +189,11 @@ int bioim_id_eval(bioim_handle_t *h, int op, int n, const void *q, const void *u
  *    per CoordinateLimitForce: its generalized force,
  *    calc_cost_of_transport() (0 for torque models)].
  * Env-level state (action deque, last action, old pelvis x, done) is left
- * alone.  Refused while envs are suspended mid-step (bioim_set_rk_budget).
+ * alone.  A REALIZE, with or without controls, reads the state and leaves
+ * the next bioim_step's results bit for bit what they are without it (the
+ * realize cache stays valid); EQUILIBRATE and INTEGRATE move the state and
+ * mark the handle's realize-cache rows stale.
+ * Refused while envs are suspended mid-step (bioim_set_rk_budget).
  * Asynchronous on the handle's stream. */
 enum {
     BIOIM_OSIM_REALIZE = 0,
@@ -357,6 +362,23 @@ uint64_t bioim_modelpack_size(void);
  * refuses a library whose id differs from its source tree's.  No reference
  * counterpart (build hygiene). */
 const char *bioim_build_id(void);
+
+/* ---- debug / tests ---- */
+/* One whole plane of the per-env record, by the name of its DState member
+ * (q, u, act, lce, hist, last, old_px, t, istep, has_last, done, resets, hrk,
+ * pend, rkt, rkh, rka, ctl, cur, vnw, rkev, cache, cache_ok), copied
+ * device -> host, or host -> device when `write` is not 0.  Synchronizes both
+ * of the handle's streams first.  The plane is raw device memory:
+ * [count][N] with the env index fastest (the cache: [N][cache_dim] rows), in
+ * the handle's precision for the real-valued planes (t, hrk, rkt, rkh are
+ * doubles; the flags and counters int32; rkev uint64).  `bytes` must be the
+ * plane's exact size; an unknown name, a null handle or buffer or another
+ * size returns BIOIM_E_ARG before any device call.  For tests of what the
+ * flat state row does not show (the realize cache and its flags, the warm
+ * starts, a suspended RK step, the counters); a write is taken as is, so a
+ * caller can leave an env's record inconsistent on purpose.  No reference
+ * counterpart. */
+int bioim_debug_plane(bioim_handle_t *h, const char *name, void *host, size_t bytes, int write);
 
 #ifdef __cplusplus
 }

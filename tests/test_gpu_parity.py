@@ -1098,8 +1098,10 @@ def test_realize_cache_first_substep(env_id):
     arithmetic at the substep's h; the actuator torques are added the same
     way); muscle models agree to the rounding level and differ somewhere (the
     first substep's fiber-velocity roots are the realize's warm-started ones
-    instead of a cold start: the cached path really ran).  The cached run
-    stays within the usual bound of the oracle."""
+    instead of a cold start: the cached path really ran; for torque models
+    tests/test_gpu_realize_cache.py shows it with swapped cache rows, and
+    covers the other ways the cache is invalidated).  The cached run stays
+    within the usual bound of the oracle."""
     import torch
     from bioimitation.vector_env import VectorEnv
     import oracle
@@ -1137,6 +1139,9 @@ def test_realize_cache_first_substep(env_id):
         assert differs, 'the cached first substep never ran (results bit-equal to the uncached run)'
         assert worst_ab < 5e-9, worst_ab   # observed 2.9e-10 (2D), 1.1e-9 (Running3D)
     else:
+        # bit-equal also if the cache were never used (e.g. cache_h never equal to dt): that the torque
+        # models' cached first substep really runs is shown by
+        # test_gpu_realize_cache.py::test_b_swapped_rows_show_the_cached_path_runs
         assert not differs, worst_ab
     assert worst_orc < 1e-6, worst_orc
     a.close()

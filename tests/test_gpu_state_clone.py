@@ -300,7 +300,11 @@ def test_validation_refuses_on_the_host():
         a.load_state(two)                      # 2 rows for all 35 envs
     for out in (torch.zeros((N, a.state_dim), dtype=torch.float32, device=a.device),
                 torch.zeros((N - 1, a.state_dim), dtype=torch.float64, device=a.device),
-                torch.zeros((N, a.state_dim), dtype=torch.float64)):
+                torch.zeros((N, a.state_dim), dtype=torch.float64),                                   # on the host
+                torch.zeros((N, a.state_dim + 1), dtype=torch.float64, device=a.device)[:, :-1],      # row stride
+                torch.zeros((N, 2 * a.state_dim), dtype=torch.float64, device=a.device)[:, ::2],      # not contiguous
+                torch.zeros((a.state_dim, N), dtype=torch.float64, device=a.device),                  # transposed shape
+                np.zeros((N, a.state_dim))):
         with pytest.raises(ValueError, match='state_rows: out must be a contiguous'):
             a.state_rows(out=out)
     with pytest.raises(ValueError, match='state_rows: out'):

@@ -72,6 +72,18 @@ def test_null_buffers_and_bad_n_are_argument_errors():
     assert b'null src or dst' in L.bioim_last_error()
     assert L.bioim_clone_envs(h, idp, None, 1) == -1
     assert b'null src or dst' in L.bioim_last_error()
+    # bioim_debug_plane (debug / tests): the name, the buffer and the size are checked first
+    dbg = L.bioim_debug_plane
+    assert dbg(None, b'cache_ok', buf, 0, 0) == -1
+    assert b'bioim_debug_plane: null handle' in L.bioim_last_error()
+    assert dbg(h, None, buf, 0, 0) == -1 and dbg(h, b'cache_ok', None, 0, 0) == -1
+    assert b'null plane name or host buffer' in L.bioim_last_error()
+    for write in (0, 1):
+        assert dbg(h, b'cache_okay', buf, 0, write) == -1
+        assert b"no plane named 'cache_okay'" in L.bioim_last_error()
+        for name in (b'cache', b'cache_ok', b'vnw', b'ctl', b'pend', b'resets', b'rkev'):
+            assert dbg(h, name, buf, 64, write) == -1     # a handle of 0 envs: every plane holds 0 bytes
+            assert b'holds 0 bytes, the buffer 64' in L.bioim_last_error()
     for n in (0, -3, 4):        # none, negative, more than the handle's envs
         assert L.bioim_copy_state_rows(h, idp, n, buf) == -1
         assert b'bioim_copy_state_rows: n must lie in' in L.bioim_last_error()
