@@ -77,6 +77,7 @@ class VectorEnv:
         self.launch = dict(lanes_per_env=ql[0], threads_per_workgroup=ql[1], envs_per_workgroup=ql[2],
                            lds_bytes_per_workgroup=ql[3], workgroups=ql[4])
         _lib.check(L.bioim_set_auto_reset(h, 1 if auto_reset else 0))
+        self._auto_reset = bool(auto_reset)
         # config 'integrator': 'semi-implicit' (fixed substeps, the default) or 'rk-merson' (the
         # reference's adaptive integrator at 'integrator_accuracy', default the env's 1e-3)
         self.integrator = (config or {}).get('integrator', 'semi-implicit')
@@ -286,6 +287,7 @@ class VectorEnv:
 
     def set_auto_reset(self, on: bool):
         _lib.check(self._L.bioim_set_auto_reset(self._h, 1 if on else 0))
+        self._auto_reset = bool(on)
 
     def reset(self, env_ids=None, ref_index=None):
         """Reset the listed envs (default all).  ref_index: reference rows
@@ -319,6 +321,92 @@ class VectorEnv:
         _lib.check(self._L.bioim_step(self._h, self._ptr(a), self._ptr(self.obs), self._ptr(self.reward),
                                       self._ptr(self.done), self._ptr(self.info)))
         return self.obs, self.reward, self.done, self.info
+
+    def _check_seq(self, t, shape, dtype, what):
+        """a caller buffer the rollout writes prod(shape) elements through"""
+        import torch
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype != dtype \
+                or t.device != self.device or not t.is_contiguous():
+            raise ValueError(f'rollout: {what} must be a contiguous {tuple(shape)} {dtype} tensor on {self.device}')
+        return t
+
+    def rollout(self, actions, steps=None, *, obs='last', info=False, stop_at_done=False, out=None):
+        """T consecutive env steps from an action sequence, enqueued by one
+        call with nothing on the host in between (``bioim_rollout``): with the
+        default step configuration one kernel launch, otherwise (push table,
+        'rk-merson', force report, state storage) T launches from C — see
+        ``last_rollout_fused``.  Bit for bit what T ``step()`` calls give.
+
+        ``actions``: (T, N, A), or (N, A) with ``steps=T`` to repeat one action
+        block (frame skip); dtype / device / contiguity as in ``step()``.
+        ``obs``: 'last' (the last step's rows, written to ``self.obs``, so a
+        following ``step()`` composes as usual), 'all' ((T, N, O); ``self.obs``
+        gets the last rows too) or None.  ``info``: also the (T, N, I) rows.
+        ``stop_at_done`` (auto-reset off only): an env is not stepped again
+        after its first done; its later rows are reward 0, done 1, info 0 and
+        its terminal observation.  The active mask is honoured and left alone.
+        ``out``: a dict of caller buffers to write to instead of new tensors —
+        'reward' (T, N), 'done' (T, N) uint8, 'obs' (T, N, O) with obs='all',
+        'info' (T, N, I); contiguous, of the env's dtype, on its device.
+
+        Returns (obs, reward (T, N), done (T, N) uint8, info or None)."""
+        import torch
+        if obs not in ('last', 'all', None):
+            raise ValueError(f"rollout: obs must be 'last', 'all' or None, got {obs!r}")
+        if not isinstance(actions, torch.Tensor):
+            raise ValueError('rollout: actions must be a torch tensor')
+        n, na = self.num_envs, self.action_dim
+        if actions.dim() == 2:
+            if steps is None:
+                raise ValueError('rollout: (N, A) actions need steps=T')
+            T, stride = int(steps), 0
+            want = (n, na)
+        else:
+            T = int(actions.shape[0]) if actions.dim() == 3 else 0
+            if steps is not None and int(steps) != T:
+                raise ValueError(f'rollout: steps={steps} but actions hold {T} steps')
+            stride = n * na
+            want = (T, n, na)
+        if T <= 0 or tuple(actions.shape) != want:
+            raise ValueError(f'rollout: actions must have shape (T, {n}, {na}) or ({n}, {na}) with steps=T >= 1, '
+                             f'got {tuple(actions.shape)}')
+        if stop_at_done and self._auto_reset:
+            raise ValueError('rollout: stop_at_done needs auto-reset off')
+        a = actions
+        if a.dtype != self.dtype or a.device != self.device or not a.is_contiguous():
+            a = a.to(device=self.device, dtype=self.dtype).contiguous()
+        out = dict(out or {})
+        unknown = set(out) - {'obs', 'reward', 'done', 'info'}
+        if unknown:
+            raise ValueError(f'rollout: unknown out buffers {sorted(unknown)}')
+        shapes = {'reward': ((T, n), self.dtype), 'done': ((T, n), torch.uint8)}
+        if obs == 'all':
+            shapes['obs'] = ((T, n, self.obs_dim), self.dtype)
+        if info:
+            shapes['info'] = ((T, n, self.info_dim), self.dtype)
+        for k in out:
+            if k not in shapes:
+                raise ValueError(f"rollout: out['{k}'] given but not asked for (obs={obs!r}, info={info})")
+        buf = {}
+        for k, (shape, dtype) in shapes.items():
+            if k in out:
+                buf[k] = self._check_seq(out[k], shape, dtype, f"out['{k}']")
+            else:
+                buf[k] = torch.empty(shape, dtype=dtype, device=self.device)
+        obs_seq, obs_last = buf.get('obs'), (self.obs if obs is not None else None)
+        if getattr(self, '_storage_grow', 0):
+            self._apply_storage_growth()
+        self._bind_stream()
+        _lib.check(self._L.bioim_rollout(self._h, self._ptr(a), T, stride, self._ptr(obs_seq), self._ptr(obs_last),
+                                         self._ptr(buf['reward']), self._ptr(buf['done']), self._ptr(buf.get('info')),
+                                         1 if stop_at_done else 0))
+        return (self.obs if obs == 'last' else obs_seq), buf['reward'], buf['done'], buf.get('info')
+
+    @property
+    def last_rollout_fused(self) -> bool:
+        """True if the last ``rollout()`` ran as ONE launch of the rollout
+        kernel, False if it looped over the step kernels (bioim_rollout_fused)."""
+        return bool(_lib.check(self._L.bioim_rollout_fused(self._h)))
 
     def get_state(self) -> np.ndarray:
         s = np.zeros((self.num_envs, self.state_dim))

@@ -3700,6 +3700,152 @@ __global__ __launch_bounds__(BIOIM_EPB * T0::G) __attribute__((amdgpu_waves_per_
     else env_block<T1, Real, false, false, false>(a1, blockIdx.x - a0.blocks);
 }
 
+/* Fused multi-step rollout (bioim_rollout): `steps` consecutive env steps of
+ * the default step kernel's code in ONE launch.  Envs never talk to each
+ * other and a lane group loads its env's record, advances it and stores it
+ * back, so step k+1 of an env needs only what its own workgroup wrote in step
+ * k: no grid-wide synchronisation.  a0 holds step 0's arguments; step k runs
+ * env_block on a copy with the I/O pointers at that step's slices. */
+template <typename Real> struct RolloutSeq {
+    int steps, stop_at_done;
+    int64_t act_step;      /* elements between two steps' action blocks (0: the same actions every step) */
+    Real *obs_seq;         /* optional [steps][N][obs_stride] */
+    Real *obs_last;        /* optional [N][obs_stride]: the last step's rows */
+    Real *reward_seq;      /* optional [steps][N] */
+    uint8_t *done_seq;     /* [steps][N] */
+    Real *info_seq;        /* optional [steps][N][info_stride] */
+    uint8_t *live;         /* stop_at_done: per-handle scratch mask [N], this launch's active mask */
+    const uint8_t *active; /* the caller's active mask (bioim_set_active_mask) or null */
+};
+
+/* step k's view of the launch arguments */
+template <class T, typename Real>
+DEV LaunchArgs<T, Real> rollout_step_args(const LaunchArgs<T, Real> &a0, const RolloutSeq<Real> &r, int k) {
+    LaunchArgs<T, Real> a = a0;
+    const size_t N = (size_t)a0.N;
+    a.actions = a0.actions + (size_t)k * (size_t)r.act_step;
+    /* without a sequence buffer the observation goes to obs_last: from the
+     * last step only, or from every step when envs can freeze at their
+     * terminal one (stop_at_done) */
+    a.obs = r.obs_seq ? r.obs_seq + (size_t)k * N * a0.obs_stride
+                      : (k == r.steps - 1 || r.stop_at_done ? r.obs_last : nullptr);
+    a.reward = r.reward_seq ? r.reward_seq + (size_t)k * N : nullptr;
+    a.done_out = r.done_seq + (size_t)k * N;
+    a.info = r.info_seq ? r.info_seq + (size_t)k * N * a0.info_stride : nullptr;
+    if (r.stop_at_done) a.active = r.live;
+    return a;
+}
+
+/* This thread's lane in its env's group and the env, for the rollout loop's
+ * bookkeeping — not from threadIdx: that register would be live across the
+ * step code, where the register allocator may park a value in an AGPR under
+ * the narrowed EXEC that follows env_block's early returns, with the lanes
+ * that returned left out (the hazard of DESIGN.md 5.5; a frozen env's lanes
+ * are such lanes, and they store rows afterwards).  The wave's index in the
+ * workgroup is a scalar, which EXEC does not touch; the lane's index in the
+ * wave is counted anew where it is needed, in full EXEC. */
+DEV int rollout_wave() { return __builtin_amdgcn_readfirstlane((int)threadIdx.x) >> 6; }   /* at kernel entry: every lane active */
+template <class T> DEV void rollout_thread(int wave, int &lane, int &env) {
+    static_assert(BIOIM_EPB * T::G % 64 == 0, "whole waves");
+    /* (as volatile asm: the mbcnt builtins are pure, so the compiler counts
+     * once at kernel entry and carries the result through the step code) */
+    int in_wave;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(in_wave));
+    const int tid = wave * 64 + in_wave;
+    lane = tid % T::G;
+    env = blockIdx.x * BIOIM_EPB + tid / T::G;
+}
+
+template <class T, typename Real>
+__global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_eu(1, 1))) void rollout_kernel(
+    LaunchArgs<T, Real> a0, RolloutSeq<Real> r) {
+    constexpr int G = T::G;
+    static_assert(G <= 64, "an env's lane group lies in one wave (the mask below is read, then cleared, in program order)");
+    /* stop_at_done: this launch's mask starts as the caller's (or all ones);
+     * an env the caller masked out is never touched, a live one leaves the
+     * mask after its first done */
+    const int wave = rollout_wave();
+    if (r.stop_at_done) {
+        int lane, env;
+        rollout_thread<T>(wave, lane, env);
+        if (env < a0.N && lane == 0) r.live[env] = !r.active || r.active[env] != 0 ? 1 : 0;
+    }
+    /* The loop over the steps is written with a second, never-taken entry
+     * (steps > 0 is bioim_rollout's contract), so that the optimizer does not
+     * see a natural loop: as one it moved the step code's thread-only values
+     * (a hundred lane-derived indices, masks and LDS offsets, which env_block
+     * forms from threadIdx) in front of the loop and kept them in registers
+     * across the whole step body, and the fp64 spatial muscle kernels spilled
+     * to scratch.  Values it could still move that way are made opaque below. */
+    int k = 0, blk = blockIdx.x;
+    LaunchArgs<T, Real> a = a0;
+    if (r.steps <= 0) goto meet;
+step:
+    {
+        a = rollout_step_args<T, Real>(a0, r, k);
+        /* each step's block index, env count, model and plane pointers are
+         * opaque to the compiler: otherwise it forms the step's
+         * loop-invariant address parts (a 64-bit pair per state plane and
+         * lane: plane + index * N) and model constants once, ahead of the
+         * steps, and keeps them in registers across the whole step body */
+        blk = blockIdx.x;
+        asm volatile("" : "+s"(blk));
+        asm volatile("" : "+s"(a.N));
+        asm volatile("" : "+s"(a.Mg));
+        asm volatile("" : "+s"(a.Sg));
+        asm volatile("" : "+s"(a.act_stride), "+s"(a.obs_stride), "+s"(a.info_stride));
+        asm volatile("" : "+s"(a.st.q), "+s"(a.st.u), "+s"(a.st.act), "+s"(a.st.lce), "+s"(a.st.hist), "+s"(a.st.last));
+        asm volatile("" : "+s"(a.st.vnw), "+s"(a.st.cache), "+s"(a.st.cache_ok));
+        /* every thread makes every call: env_block holds a workgroup barrier
+         * (before it reads the mask) and returns early only after it */
+        env_block<T, Real, false, false, false>(a, blk);
+    }
+meet:
+    {
+        /* step k+1 reads what step k stored through global memory (state
+         * planes, realize-cache row, cache_ok, the mask): release the stores,
+         * meet, acquire — at workgroup scope, the env's lanes share one CU */
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __syncthreads();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        if (r.stop_at_done) {
+            int lane, env;
+            rollout_thread<T>(wave, lane, env);
+            if (env < a0.N && (!r.active || r.active[env] != 0)) {
+                if (r.live[env]) {   /* stepped just now */
+                    if (a.done_out[env] && lane == 0) r.live[env] = 0;
+                } else {
+                    /* a frozen env's later rows: reward 0, done 1, info 0, and
+                     * its terminal observation again */
+                    if (lane == 0) {
+                        if (a.reward) a.reward[env] = Real(0);
+                        a.done_out[env] = 1;
+                    }
+                    if (a.info && lane < a0.Mg->info_dim) a.info[(size_t)env * a0.info_stride + lane] = Real(0);
+                    if (r.obs_seq) {
+                        Real *row = a.obs + (size_t)env * a0.obs_stride;
+                        const Real *prev = row - (size_t)a0.N * a0.obs_stride;
+                        for (int j = lane; j < a0.Mg->obs_dim; j += G) row[j] = prev[j];
+                    }
+                }
+            }
+        }
+        if (++k < r.steps) goto step;
+    }
+    /* with a sequence buffer the last rows also go to obs_last (envs the step
+     * left untouched keep theirs, as with bioim_step); the rows were stored
+     * before the loop's last barrier */
+    if (r.obs_seq && r.obs_last) {
+        int lane, env;
+        rollout_thread<T>(wave, lane, env);
+        if (env < a0.N && (!a0.active || a0.active[env] != 0)) {
+            const Real *last = r.obs_seq + ((size_t)(r.steps - 1) * a0.N + env) * a0.obs_stride;
+            Real *row = r.obs_last + (size_t)env * a0.obs_stride;
+            for (int j = lane; j < a0.Mg->obs_dim; j += G) row[j] = last[j];
+        }
+    }
+}
+
 #define BIOIM_FUSED_PAIRS(X)                                                         \
     X(Topo_MuscleLockedKneeImitation3D_v0, Topo_MuscleWalkingImitation3D_v0)          \
     X(Topo_MuscleWalkingImitation3D_v0, Topo_MuscleLockedKneeImitation3D_v0)
@@ -4097,6 +4243,16 @@ struct OsimCall {   /* mode 2 launch arguments (bioim_osim) */
     void *report;
 };
 
+struct RolloutCall {   /* bioim_rollout's arguments (untyped), for Ops::rollout */
+    const void *actions;
+    int steps;
+    int64_t act_step;
+    void *obs_seq, *obs_last, *reward_seq;
+    uint8_t *done_seq;
+    void *info_seq;
+    int stop_at_done;
+};
+
 struct Ops {
     const char *topo;   /* the topology struct's name (fused-pair lookup) */
     int lanes;
@@ -4106,6 +4262,9 @@ struct Ops {
     void (*launch)(bioim_handle_t *, int mode, const void *actions, void *obs, void *reward, uint8_t *done, void *info,
                    const int32_t *env_ids, const int32_t *ref_index, int n_list, const OsimCall *oc);
     void (*id_launch)(bioim_handle_t *, int op, int n, const void *q, const void *u, const void *v, void *out);
+    /* the fused rollout kernel's launcher; null where that instantiation is
+     * left out (bioim_rollout then loops over `launch`) */
+    void (*rollout)(bioim_handle_t *, const RolloutCall &);
 };
 
 struct bioim_handle {
@@ -4138,6 +4297,8 @@ struct bioim_handle {
     int planar;           /* the pack's topology is planar (pack_is_planar) */
     int reset_tab_on;     /* bioim_set_reset_table (default 1) */
     int cache_live;       /* a default step kernel ran since the realize-cache flags were last cleared */
+    uint8_t *rollout_live; /* bioim_rollout stop_at_done: scratch mask [n], allocated on first use */
+    int last_rollout_fused; /* the last bioim_rollout ran as one launch of the rollout kernel */
     Ops ops;
     bioim_modelpack_t pack;
 };
@@ -4285,6 +4446,23 @@ int fused_launch_impl(bioim_handle_t *h0, bioim_handle_t *h1, const void *action
     return 0;
 }
 
+/* one launch of rollout_kernel: the default step configuration only
+ * (bioim_rollout checks it), on the handle's stream */
+template <class T, typename Real>
+void rollout_launch_impl(bioim_handle_t *h, const RolloutCall &c) {
+    LaunchArgs<T, Real> a = make_args<T, Real>(h, 0, c.actions, nullptr, nullptr, c.done_seq, nullptr, nullptr, nullptr, 0, nullptr);
+    if (a.blocks <= 0) return;
+    RolloutSeq<Real> r;
+    r.steps = c.steps; r.stop_at_done = c.stop_at_done; r.act_step = c.act_step;
+    r.obs_seq = reinterpret_cast<Real *>(c.obs_seq); r.obs_last = reinterpret_cast<Real *>(c.obs_last);
+    r.reward_seq = reinterpret_cast<Real *>(c.reward_seq); r.done_seq = c.done_seq;
+    r.info_seq = reinterpret_cast<Real *>(c.info_seq);
+    r.live = h->rollout_live; r.active = h->active;
+    if constexpr (CacheLay<T>::ON) h->cache_live = 1;   /* default step code: it forms the realize cache */
+    constexpr size_t lds = lds_bytes<T, Real, false>();
+    hipLaunchKernelGGL((rollout_kernel<T, Real>), dim3(a.blocks), dim3(BIOIM_EPB * T::G), lds, h->stream, a, r);
+}
+
 template <class T, typename Real>
 void id_launch_impl(bioim_handle_t *h, int op, int n, const void *q, const void *u, const void *v, void *out) {
     constexpr int EPB = BIOIM_EPB;
@@ -4318,6 +4496,8 @@ template <class T, typename Real> int upload_smodel(bioim_handle_t *h) {
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, Real, true>()));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&id_kernel<T, Real>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, Real, false>()));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&rollout_kernel<T, Real>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, Real, false>()));
     constexpr size_t B = smodel_bytes<T, Real>();
     std::vector<unsigned char> img(B, 0);
     build_smodel<T, Real>(h->pack, *reinterpret_cast<SModel<T, Real> *>(img.data()));
@@ -4337,11 +4517,13 @@ template <class T> bool pick(const bioim_modelpack_t &p, int precision, Ops &ops
         ops.launch = &launch_impl<T, double>;
         ops.id_launch = &id_launch_impl<T, double>;
         ops.upload = &upload_smodel<T, double>;
+        ops.rollout = &rollout_launch_impl<T, double>;
         ops.lds_bytes = lds_bytes<T, double>();
     } else {
         ops.launch = &launch_impl<T, float>;
         ops.id_launch = &id_launch_impl<T, float>;
         ops.upload = &upload_smodel<T, float>;
+        ops.rollout = &rollout_launch_impl<T, float>;
         ops.lds_bytes = lds_bytes<T, float>();
     }
     return true;
@@ -4531,6 +4713,7 @@ int bioim_create(const bioim_modelpack_t *pack, int n_envs, int device, int prec
     h->env_offset = 0;
     h->pert_n = 0; h->pert_ob = -1;
     h->reset_tab = nullptr; h->reset_tab_on = 1; h->cache_live = 0;
+    h->rollout_live = nullptr; h->last_rollout_fused = 0;
     h->planar = pack_is_planar(*pack) ? 1 : 0;
     h->act_stride = pack->nact; h->obs_stride = pack->obs_dim; h->info_stride = pack->info_dim;
     h->ops = ops;
@@ -4565,6 +4748,7 @@ int bioim_destroy(bioim_handle_t *h) {
     if (h->pert_x) hipFree(h->pert_x);
     if (h->pert_y) hipFree(h->pert_y);
     if (h->reset_tab) hipFree(h->reset_tab);
+    if (h->rollout_live) hipFree(h->rollout_live);
     if (h->dstate) {
         if (h->precision == 64) delete reinterpret_cast<DState<double> *>(h->dstate);
         else delete reinterpret_cast<DState<float> *>(h->dstate);
@@ -5371,6 +5555,121 @@ int bioim_debug_stamps(unsigned long long *out, int reset) {
     return 0;
 }
 #endif
+
+/* bioim_rollout's host-loop path (push table, RK-Merson, force report, state
+ * storage, or no rollout kernel for the topology): the existing step kernels,
+ * one launch per step.  The three small kernels below do between those
+ * launches what rollout_kernel does in its loop; one thread per env (per
+ * observation value for the copy), sizes as run-time arguments.
+ * rollout_live_init: the stop_at_done mask starts as the caller's mask (or
+ * ones).  rollout_freeze_kernel, after step k: a live env that returned done
+ * leaves the mask; an env that left it earlier gets its frozen rows.
+ * rollout_obs_last_kernel: the last rows of obs_seq also go to obs_last,
+ * except for envs the caller masked out. */
+extern "C++" {
+__global__ void rollout_live_init(uint8_t *live, const uint8_t *active, int n) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < n) live[e] = !active || active[e] != 0 ? 1 : 0;
+}
+
+template <typename Real>
+__global__ void rollout_freeze_kernel(uint8_t *live, const uint8_t *active, int n, uint8_t *done, Real *reward, Real *info,
+                                      int info_dim, int info_stride, Real *obs, const Real *obs_prev, int obs_dim,
+                                      int obs_stride) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n || (active && active[e] == 0)) return;
+    if (live[e]) {
+        if (done[e]) live[e] = 0;
+        return;
+    }
+    if (reward) reward[e] = Real(0);
+    done[e] = 1;
+    if (info)
+        for (int j = 0; j < info_dim; ++j) info[(size_t)e * info_stride + j] = Real(0);
+    if (obs && obs_prev)
+        for (int j = 0; j < obs_dim; ++j) obs[(size_t)e * obs_stride + j] = obs_prev[(size_t)e * obs_stride + j];
+}
+
+template <typename Real>
+__global__ void rollout_obs_last_kernel(const uint8_t *active, int n, const Real *obs, Real *obs_last, int obs_dim,
+                                        int obs_stride) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n * obs_dim) return;
+    const size_t e = i / obs_dim, at = e * obs_stride + i % obs_dim;
+    if (!active || active[e] != 0) obs_last[at] = obs[at];
+}
+
+template <typename Real> static void rollout_host_loop(bioim_handle_t *h, const RolloutCall &c) {
+    const size_t n = (size_t)h->n;
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    const Real *actions = reinterpret_cast<const Real *>(c.actions);
+    Real *obs_seq = reinterpret_cast<Real *>(c.obs_seq), *obs_last = reinterpret_cast<Real *>(c.obs_last);
+    Real *reward_seq = reinterpret_cast<Real *>(c.reward_seq), *info_seq = reinterpret_cast<Real *>(c.info_seq);
+    const uint8_t *const user_active = h->active;
+    if (c.stop_at_done) {
+        hipLaunchKernelGGL(rollout_live_init, dim3(blocks), dim3(256), 0, h->stream, h->rollout_live, user_active, (int)n);
+        h->active = h->rollout_live;
+    }
+    for (int k = 0; k < c.steps; ++k) {
+        Real *obs = obs_seq ? obs_seq + (size_t)k * n * h->obs_stride
+                            : (k == c.steps - 1 || c.stop_at_done ? obs_last : nullptr);
+        Real *reward = reward_seq ? reward_seq + (size_t)k * n : nullptr;
+        uint8_t *done = c.done_seq + (size_t)k * n;
+        Real *info = info_seq ? info_seq + (size_t)k * n * h->info_stride : nullptr;
+        h->ops.launch(h, 0, actions + (size_t)k * (size_t)c.act_step, obs, reward, done, info, nullptr, nullptr, 0, nullptr);
+        if (c.stop_at_done)
+            hipLaunchKernelGGL((rollout_freeze_kernel<Real>), dim3(blocks), dim3(256), 0, h->stream, h->rollout_live,
+                               user_active, (int)n, done, reward, info, h->info_dim, h->info_stride,
+                               obs_seq ? obs : nullptr, obs_seq && k > 0 ? obs - n * h->obs_stride : nullptr, h->obs_dim,
+                               h->obs_stride);
+    }
+    h->active = user_active;
+    if (obs_seq && obs_last)
+        hipLaunchKernelGGL((rollout_obs_last_kernel<Real>), dim3((unsigned)((n * h->obs_dim + 255) / 256)), dim3(256), 0,
+                           h->stream, user_active, (int)n, obs_seq + (size_t)(c.steps - 1) * n * h->obs_stride, obs_last,
+                           h->obs_dim, h->obs_stride);
+}
+}  // extern "C++"
+
+/* the configurations rollout_kernel covers: the default step kernel's
+ * (semi-implicit, no push table) without a force report or state storage */
+static inline bool rollout_fusable(const bioim_handle_t *h) {
+    return h->ops.rollout && !h->rk && h->pert_n == 0 && !h->force_out && !h->traj;
+}
+
+int bioim_rollout(bioim_handle_t *h, const void *actions, int steps, int64_t action_step_stride, void *obs_seq,
+                  void *obs_last, void *reward_seq, uint8_t *done_seq, void *info_seq, int stop_at_done) {
+    if (!h) return fail(BIOIM_E_ARG, "bioim_rollout: null handle");
+    if (!actions || !done_seq) return fail(BIOIM_E_ARG, "bioim_rollout: null actions or done_seq");
+    if (steps <= 0) return fail(BIOIM_E_ARG, "bioim_rollout: steps must be positive");
+    if (action_step_stride < 0) return fail(BIOIM_E_ARG, "bioim_rollout: negative action_step_stride");
+    if (h->rk && h->rk_budget > 0)
+        return fail(BIOIM_E_ARG, "bioim_rollout: a budgeted RK handle suspends envs mid-step, a rollout has no rows for that "
+                                 "(bioim_set_rk_budget(h, 0, NULL) first)");
+    if (stop_at_done && h->auto_reset)
+        return fail(BIOIM_E_ARG, "bioim_rollout: stop_at_done needs auto-reset off (a reset env goes on)");
+    HIPCHK(hipSetDevice(h->device));
+    if (h->rk) {   /* only an RK handle can hold suspended envs; the count waits for its stream */
+        const int np = bioim_pending_count(h);
+        if (np < 0) return np;
+        if (np > 0) return fail(BIOIM_E_ARG, "bioim_rollout: envs are suspended mid-step (bioim_set_rk_budget)");
+    }
+    if (const int rc = ensure_reset_table(h)) return rc;
+    if (stop_at_done && !h->rollout_live) HIPCHK(hipMalloc(reinterpret_cast<void **>(&h->rollout_live), (size_t)h->n));
+    const RolloutCall c{actions, steps, action_step_stride, obs_seq, obs_last, reward_seq, done_seq, info_seq,
+                        stop_at_done ? 1 : 0};
+    h->last_rollout_fused = rollout_fusable(h) ? 1 : 0;
+    if (h->last_rollout_fused) h->ops.rollout(h, c);
+    else if (h->precision == 64) rollout_host_loop<double>(h, c);
+    else rollout_host_loop<float>(h, c);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int bioim_rollout_fused(const bioim_handle_t *h) {
+    if (!h) return fail(BIOIM_E_ARG, "bioim_rollout_fused: null handle");
+    return h->last_rollout_fused ? 1 : 0;
+}
 
 int bioim_sync(bioim_handle_t *h) {
     if (!h) return fail(BIOIM_E_ARG, "null handle");

@@ -261,6 +261,49 @@ int bioim_load_state(bioim_handle_t *h, const int32_t *env_ids, int n, const voi
  * be a src (the caller's contract: a violation races on that env's record,
  * it does not leave the state buffer).  One launch. */
 int bioim_clone_envs(bioim_handle_t *h, const int32_t *src_ids, const int32_t *dst_ids, int n);
+/* bioim_rollout: `steps` consecutive env steps from an action sequence, for
+ * shooting planners, population branching (after bioim_clone_envs) and action
+ * repeat.  Every pointer is a device pointer on the handle's device, in the
+ * handle's precision and I/O strides:
+ *   actions: step k reads [N][act_stride] at actions + k * action_step_stride
+ *     elements; a stride of 0 repeats the same actions every step (frame skip);
+ *   reward_seq [steps][N] (may be NULL); done_seq [steps][N] (required);
+ *   obs_seq (may be NULL) [steps][N][obs_stride];
+ *   obs_last (may be NULL) [N][obs_stride]: the last step's rows only;
+ *   info_seq (may be NULL) [steps][N][info_stride].
+ * State and every output are bit for bit those of `steps` bioim_step calls on
+ * the same slices: in-kernel auto-resets (reset-table rows, device-drawn
+ * rows, reset counters), the realize cache, the active mask (a masked-out
+ * env's rows are left as they are) and final_obs, which keeps the last
+ * step's values.  The reset table is built before the launch, as on
+ * bioim_step's first step.  Asynchronous on the handle's stream; apart from
+ * that one-time table build (and the first stop_at_done call's allocation of
+ * its mask) nothing is synchronized on the default path.
+ * stop_at_done (auto-reset off only): an env whose step k returned done is
+ * not stepped again in this call — its state stays the one right after that
+ * step, its later rows are reward 0, done 1, info 0 and its terminal
+ * observation again (obs_last holds the terminal one).  The caller's active
+ * mask is read, never written: the call keeps its own mask per handle.
+ * Paths: with the default step configuration (semi-implicit, no push table,
+ * no force report, no state storage) the whole call is ONE launch of the
+ * rollout kernel, which runs the step kernel's code in a loop (step k+1 of
+ * an env reads only what its own workgroup stored in step k), and
+ * bioim_rollout_fused returns 1.  With a push table, unbudgeted RK-Merson, a
+ * force report or state storage the same call enqueues `steps` launches of
+ * the step kernels from C (results identical, bioim_rollout_fused returns 0;
+ * an RK handle's check for suspended envs waits for its stream).
+ * Refused with BIOIM_E_ARG and a message before any device call: a null
+ * handle, null actions or done_seq, steps <= 0, a negative stride, a budgeted
+ * RK handle (rk_budget > 0: a suspended step has no per-step rows) or one
+ * with suspended envs, stop_at_done with auto-reset on.  The buffers' sizes
+ * are the caller's contract (VectorEnv.rollout checks them).  No reference
+ * counterpart (one OsimModel steps one env from Python). */
+int bioim_rollout(bioim_handle_t *h, const void *actions, int steps, int64_t action_step_stride,
+                  void *obs_seq, void *obs_last, void *reward_seq, uint8_t *done_seq, void *info_seq,
+                  int stop_at_done);
+/* 1 if the last bioim_rollout on h ran as one launch of the rollout kernel, 0
+ * if it looped over the step kernels (or none ran yet); -1 for a null handle. */
+int bioim_rollout_fused(const bioim_handle_t *h);
 
 /* Integrator of the physics between env steps.  kind 0: the fixed
  * semi-implicit substeps (the pack's nsub; default).  kind 1: the reference's

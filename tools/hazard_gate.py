@@ -1,7 +1,7 @@
 """Register-hazard gate over the BUILT kernels (CPU, seconds): the device code
 object of every libbioim.so unit (bioimitation-gym_amd/build/bioim_topo*.o) is
-unbundled and disassembled, and tools/exec_hazard.py scans every env / ID
-kernel for VGPR<->AGPR copies made under a narrowed EXEC whose value a later
+unbundled and disassembled, and tools/exec_hazard.py scans every env / ID /
+rollout kernel for VGPR<->AGPR copies made under a narrowed EXEC whose value a later
 read uses as a memory address ("masked-use+addr") or that no lane wrote
 ("undefined").  Either is the wrong-lane / fault incident class of DESIGN.md
 5.5: the r03i build faulted in such a kernel.
@@ -10,7 +10,7 @@ read uses as a memory address ("masked-use+addr") or that no lane wrote
     python tools/hazard_gate.py [build-dir] --baseline   # record the per-kernel counts (profiles/r04)
 
 The scan is conservative (it cannot tell that a later region selects a subset
-of the copy's lanes); the shipped build carries none in any of its 128
+of the copy's lanes); the shipped build carries none in any of its 142
 kernels, and tests/test_hazard_gate.py requires exactly that.
 """
 from __future__ import annotations
@@ -59,13 +59,14 @@ def kernels(lines: list[str]):
 
 
 RISKY = ('masked-use+addr', 'undefined', 'undefined+addr')
+KERNELS = ('env_kernel', 'id_kernel', 'rollout_kernel')   # the kernel templates of the per-topology and fused units
 
 
 def _scan_unit(obj):
     out = []
     with tempfile.TemporaryDirectory() as tmp:
         for name, body in kernels(disassemble(obj, tmp)):
-            if 'env_kernel' not in name and 'id_kernel' not in name:
+            if not any(k in name for k in KERNELS):
                 continue
             ins = E.parse(body)
             hits = E.scan(ins)
@@ -102,7 +103,7 @@ def _unit_resources(obj):
         cur[m.group(1)] = m.group(2)
         if {'name', 'private_segment_fixed_size', 'vgpr_count', 'agpr_count'} <= cur.keys():
             n = cur['name']
-            if 'env_kernel' in n or 'id_kernel' in n:
+            if any(k in n for k in KERNELS):
                 out[n] = (int(cur['private_segment_fixed_size']), int(cur['vgpr_count']), int(cur['agpr_count']))
             cur = {}
     return out
