@@ -22,6 +22,21 @@ MAX_REFROWS = 512
 NREFBODY = 9
 MAX_HORIZON = 8
 
+# the flat state row of bioim_get_state / bioim_copy_state, in order
+# (include/bioim.h at bioim_state_dim; g_state_row in csrc/bioim_step.hip)
+STATE_ROW_FIELDS = ('t', 'istep', 'has_last', 'old_px', 'done', 'q', 'u', 'act', 'lce', 'hist', 'last', 'hrk', 'ctl')
+
+
+def state_row_slices(ndof, nmuscle, nact, horizon):
+    """({field: slice into a flat state row}, the row's length).  ``hist`` is
+    [horizon][nact], index hh * nact + a."""
+    counts = {'q': ndof, 'u': ndof, 'act': nmuscle, 'lce': nmuscle, 'hist': horizon * nact, 'last': nact, 'ctl': nact}
+    slices, k = {}, 0
+    for f in STATE_ROW_FIELDS:
+        slices[f] = slice(k, k + counts.get(f, 1))
+        k = slices[f].stop
+    return slices, k
+
 FN_CONST, FN_LINEAR, FN_SPLINE = 0, 1, 2
 PT_FIXED, PT_COND, PT_MOVING = 0, 1, 2
 

@@ -44,7 +44,13 @@ import warnings
 
 import numpy as np
 
+from .packdef import state_row_slices
 from .storage import write_sto
+
+
+def _row_slices(pack):
+    """the named slices of the pack's flat state row (include/bioim.h)"""
+    return state_row_slices(pack.ndof, pack.nmuscle, pack.nact, pack.horizon)[0]
 
 
 class TrajectoryRecorder:
@@ -58,6 +64,7 @@ class TrajectoryRecorder:
         self.nc = pack.ncoord
         self.dof = np.array([pack.coord[c].dof for c in range(self.nc)])
         self.default = np.array([pack.coord[c].default_value for c in range(self.nc)])
+        self.row = _row_slices(pack)
         self.clear()
 
     def clear(self):
@@ -118,11 +125,7 @@ class TrajectoryRecorder:
         pk = self.pack
         nd, nm = pk.ndof, pk.nmuscle
         t = float(state_row[0])
-        qd = state_row[5:5 + nd]
-        ud = state_row[5 + nd:5 + 2 * nd]
-        act = state_row[5 + 2 * nd:5 + 2 * nd + nm]
-        lce = state_row[5 + 2 * nd + nm:5 + 2 * nd + 2 * nm]
-        full = self._full(t, qd, ud, act, lce)
+        full = self._full(t, *(state_row[self.row[f]] for f in ('q', 'u', 'act', 'lce')))
         nc = self.nc
         self._rows.append(np.concatenate([full[:1 + 2 * nc], np.asarray(qdd, dtype=np.float64), full[1 + 2 * nc:]]))
         if storage is None:
@@ -397,18 +400,19 @@ class OsimModelFacade:
         """opensim_wrapper.py:293-297: initializeState (defaults; the held
         controls stay), time 0, istep 0, reset_manager"""
         pk = self._pack
-        nd = pk.ndof
+        row = _row_slices(pk)
 
         def f(s):
             s[0] = 0.0
             s[1] = 0
+            q, u, act = s[row['q']], s[row['u']], s[row['act']]   # views of the row
             for c in range(pk.ncoord):
                 d = pk.coord[c].dof
                 if d >= 0:
-                    s[5 + d] = pk.coord[c].default_value
-                    s[5 + nd + d] = 0.0
+                    q[d] = pk.coord[c].default_value
+                    u[d] = 0.0
             for m in range(pk.nmuscle):
-                s[5 + 2 * nd + m] = pk.muscle[m].default_act
+                act[m] = pk.muscle[m].default_act
         self._edit(f)
 
     def set_time(self, t):
@@ -419,14 +423,15 @@ class OsimModelFacade:
         self._edit(f)
 
     def _set_coords(self, values: dict, speeds: bool):
-        pk, nd = self._pack, self._pack.ndof
+        pk = self._pack
+        field = _row_slices(pk)['u' if speeds else 'q']
 
         def f(s):
             for name, v in values.items():
                 c = self.coordinate_names.index(name)
                 d = pk.coord[c].dof
                 if d >= 0:              # a locked coordinate ignores setValue
-                    s[5 + (nd if speeds else 0) + d] = float(v)
+                    s[field][d] = float(v)
         self._edit(f)
 
     def set_coordinates(self, q_dict):
@@ -440,8 +445,7 @@ class OsimModelFacade:
     def actuate(self, action):
         """opensim_wrapper.py:92-107: NaN -> 0, clip, held as the controls"""
         self._call('realize', controls=action)
-        pk, nd, nm, H, na = self._pack, self._pack.ndof, self._pack.nmuscle, self._pack.horizon, self._pack.nact
-        self.last_action = self._state()[self._i, 5 + 2 * nd + 2 * nm + H * na + na + 1:][:na].copy()
+        self.last_action = self._state()[self._i, _row_slices(self._pack)['ctl']].copy()
 
     def get_last_action(self):
         return self.last_action
@@ -504,13 +508,13 @@ class OsimModelFacade:
         row — so the step's held controls come with it — and realized on a
         scratch batch (bioim_osim realize, the REP kernels), one env per row."""
         pk = self._pack
-        nd, nm = pk.ndof, pk.nmuscle
+        nd, nm, row = pk.ndof, pk.nmuscle, _row_slices(pk)
         k = len(storage)
         rz = self._realizer(k)
         S = np.tile(self._state()[self._i], (rz.num_envs, 1))
         st = np.asarray(storage, dtype=np.float64)
         S[:k, 0] = st[:, 0]
-        S[:k, 5:5 + 2 * nd + 2 * nm] = st[:, 1:1 + 2 * nd + 2 * nm]   # q u act lce: the same order
+        S[:k, row['q'].start:row['lce'].stop] = st[:, 1:1 + 2 * nd + 2 * nm]   # q u act lce: the same order
         rz.set_state(S)
         rep = rz.osim('realize', list(range(k)), want_obs=False)[:k].double().cpu().numpy()
         qdd = [split_osim_report(pk, r)['qdd'] for r in rep]

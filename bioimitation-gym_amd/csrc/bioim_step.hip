@@ -4529,109 +4529,6 @@ template <class T> bool pick(const bioim_modelpack_t &p, int precision, Ops &ops
     return true;
 }
 
-template <typename Real> size_t state_layout(bioim_handle_t *h, char *base, DState<Real> *st) {
-    size_t n = h->n, off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    size_t oq = take(sizeof(Real) * h->ndof * n), ou = take(sizeof(Real) * h->ndof * n);
-    size_t oa = take(sizeof(Real) * (h->nmuscle ? h->nmuscle : 1) * n), ol = take(sizeof(Real) * (h->nmuscle ? h->nmuscle : 1) * n);
-    size_t oh = take(sizeof(Real) * BIOIM_MAX_HORIZON * h->nact * n), olast = take(sizeof(Real) * h->nact * n);
-    size_t opx = take(sizeof(Real) * n), ot = take(sizeof(double) * n);
-    size_t oi = take(sizeof(int32_t) * n), ohl = take(sizeof(int32_t) * n), od = take(sizeof(int32_t) * n),
-           orr = take(sizeof(int32_t) * n), ohr = take(sizeof(double) * n);
-    const size_t na1 = h->nact ? h->nact : 1, nm1 = h->nmuscle ? h->nmuscle : 1;
-    size_t opd = take(sizeof(int32_t) * n), ork = take(sizeof(double) * n), orh = take(sizeof(double) * n),
-           ora = take(sizeof(int32_t) * n), octl = take(sizeof(Real) * na1 * n), ocur = take(sizeof(Real) * na1 * n),
-           ovn = take(sizeof(Real) * nm1 * n);
-    size_t oev = take(sizeof(uint64_t) * n);
-    size_t occ = take(sizeof(Real) * (size_t)cache_dim(h) * n), ocv = take(sizeof(int32_t) * n);
-    if (st) {
-        st->q = (Real *)(base + oq); st->u = (Real *)(base + ou); st->act = (Real *)(base + oa);
-        st->lce = (Real *)(base + ol); st->hist = (Real *)(base + oh); st->last = (Real *)(base + olast);
-        st->old_px = (Real *)(base + opx); st->t = (double *)(base + ot); st->istep = (int32_t *)(base + oi);
-        st->has_last = (int32_t *)(base + ohl); st->done = (int32_t *)(base + od); st->resets = (int32_t *)(base + orr);
-        st->hrk = (double *)(base + ohr);
-        st->pend = (int32_t *)(base + opd); st->rkt = (double *)(base + ork); st->rkh = (double *)(base + orh);
-        st->rka = (int32_t *)(base + ora); st->ctl = (Real *)(base + octl); st->cur = (Real *)(base + ocur);
-        st->vnw = (Real *)(base + ovn);
-        st->rkev = (uint64_t *)(base + oev);
-        st->cache = (Real *)(base + occ); st->cache_ok = (int32_t *)(base + ocv);
-    }
-    return off;
-}
-
-template <typename Real> int alloc_state(bioim_handle_t *h) {
-    size_t bytes = state_layout<Real>(h, nullptr, nullptr);
-    HIPCHK(hipMalloc(&h->state_buf, bytes));
-    HIPCHK(hipMemsetAsync(h->state_buf, 0, bytes, h->stream));
-    h->state_bytes = bytes;
-    DState<Real> *st = new DState<Real>();
-    state_layout<Real>(h, (char *)h->state_buf, st);
-    h->dstate = st;
-    DModel<Real> *hm = new DModel<Real>();
-    convert_model<Real>(h->pack, *hm);
-    HIPCHK(hipMalloc(&h->model, sizeof(DModel<Real>)));
-    HIPCHK(hipMemcpyAsync(h->model, hm, sizeof(DModel<Real>), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    delete hm;
-    return h->ops.upload(h);
-}
-
-template <typename Real> int xfer_state(bioim_handle_t *h, double *host, const double *in) {
-    DState<Real> &st = *reinterpret_cast<DState<Real> *>(h->dstate);
-    size_t n = h->n;
-    int nd = h->ndof, nm = h->nmuscle, na = h->nact, H = h->horizon;
-    std::vector<char> buf(h->state_bytes);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipStreamSynchronize(h->side));
-    HIPCHK(hipMemcpy(buf.data(), h->state_buf, h->state_bytes, hipMemcpyDeviceToHost));
-    DState<Real> hs;
-    state_layout<Real>(h, buf.data(), &hs);
-    int dim = bioim_state_dim(h);
-    if (host)
-        for (size_t e = 0; e < n; ++e)
-            if (hs.pend[e])   /* mid-step: t is the step's end time but q/u/act/lce an accepted RK point */
-                return fail(BIOIM_E_ARG, "bioim_get_state: envs are suspended mid-step by the RK budget "
-                                         "(step until bioim_pending_count() is 0)");
-    for (size_t e = 0; e < n; ++e) {
-        if (host) {
-            double *s = host + e * dim;
-            int k = 0;
-            s[k++] = hs.t[e]; s[k++] = hs.istep[e]; s[k++] = hs.has_last[e]; s[k++] = hs.old_px[e]; s[k++] = hs.done[e];
-            for (int i = 0; i < nd; ++i) s[k++] = hs.q[i * n + e];
-            for (int i = 0; i < nd; ++i) s[k++] = hs.u[i * n + e];
-            for (int i = 0; i < nm; ++i) s[k++] = hs.act[i * n + e];
-            for (int i = 0; i < nm; ++i) s[k++] = hs.lce[i * n + e];
-            for (int hh = 0; hh < H; ++hh)
-                for (int i = 0; i < na; ++i) s[k++] = hs.hist[(hh * na + i) * n + e];
-            for (int i = 0; i < na; ++i) s[k++] = hs.last[i * n + e];
-            s[k++] = hs.hrk[e];
-            for (int i = 0; i < na; ++i) s[k++] = hs.ctl[i * n + e];
-        } else {
-            const double *s = in + e * dim;
-            int k = 0;
-            hs.t[e] = s[k++]; hs.istep[e] = (int32_t)s[k++]; hs.has_last[e] = (int32_t)s[k++];
-            hs.old_px[e] = (Real)s[k++]; hs.done[e] = (int32_t)s[k++];
-            for (int i = 0; i < nd; ++i) hs.q[i * n + e] = (Real)s[k++];
-            for (int i = 0; i < nd; ++i) hs.u[i * n + e] = (Real)s[k++];
-            for (int i = 0; i < nm; ++i) hs.act[i * n + e] = (Real)s[k++];
-            for (int i = 0; i < nm; ++i) hs.lce[i * n + e] = (Real)s[k++];
-            for (int hh = 0; hh < H; ++hh)
-                for (int i = 0; i < na; ++i) hs.hist[(hh * na + i) * n + e] = (Real)s[k++];
-            for (int i = 0; i < na; ++i) hs.last[i * n + e] = (Real)s[k++];
-            hs.hrk[e] = s[k++];
-            for (int i = 0; i < na; ++i) hs.ctl[i * n + e] = (Real)s[k++];
-            hs.pend[e] = 0;   /* a state set from outside is at a step boundary */
-            hs.cache_ok[e] = 0;   /* the realize cache belongs to the state it was formed at */
-        }
-    }
-    if (in) HIPCHK(hipMemcpy(h->state_buf, buf.data(), h->state_bytes, hipMemcpyHostToDevice));
-    return 0;
-}
-
 }  // namespace
 
 /* topology k's kernel table (one object per topology, or all in this TU) */
@@ -4673,7 +4570,196 @@ BIOIM_FOR_EACH_TOPOLOGY(BIOIM_PICK_DEF)
 
 #if !defined(BIOIM_TOPO_ONLY) && !defined(BIOIM_FUSED_ONLY)
 thread_local std::string g_err;
-static bool state_planes_match(const bioim_handle_t *h);   /* with the plane table, next to bioim_copy_state */
+
+/* The per-env record: every plane of DState, described once.  The allocation
+ * (alloc_state) lays the planes out in this order and sets the DState
+ * pointers from it; the clone launch and the single-plane copies (plane_io)
+ * walk it too, so a plane added to the state has one place to be listed. */
+enum PlaneElem { PE_REAL, PE_F64, PE_I32, PE_U64 };
+enum PlaneCount { PC_ONE, PC_NDOF, PC_NM1, PC_HIST, PC_NACT, PC_NA1, PC_CACHE };   /* elements per env */
+enum PlaneLayout { PL_SOA, PL_ROWS };   /* [count][N], env fastest | [N][count], row-major per env */
+struct StatePlane {
+    const char *name;
+    size_t member;   /* offset of the plane's pointer in DState (the same for both precisions) */
+    PlaneElem elem;
+    PlaneCount count;
+    PlaneLayout layout;
+    bool cloned;
+};
+#define BIOIM_PLANE(m, elem, count, layout, cloned) {#m, __builtin_offsetof(DState<double>, m), elem, count, layout, cloned}
+static constexpr StatePlane g_state_planes[] = {
+    BIOIM_PLANE(q, PE_REAL, PC_NDOF, PL_SOA, true),
+    BIOIM_PLANE(u, PE_REAL, PC_NDOF, PL_SOA, true),
+    BIOIM_PLANE(act, PE_REAL, PC_NM1, PL_SOA, true),
+    BIOIM_PLANE(lce, PE_REAL, PC_NM1, PL_SOA, true),
+    BIOIM_PLANE(hist, PE_REAL, PC_HIST, PL_SOA, true),
+    BIOIM_PLANE(last, PE_REAL, PC_NACT, PL_SOA, true),
+    BIOIM_PLANE(old_px, PE_REAL, PC_ONE, PL_SOA, true),
+    BIOIM_PLANE(t, PE_F64, PC_ONE, PL_SOA, true),
+    BIOIM_PLANE(istep, PE_I32, PC_ONE, PL_SOA, true),
+    BIOIM_PLANE(has_last, PE_I32, PC_ONE, PL_SOA, true),
+    BIOIM_PLANE(done, PE_I32, PC_ONE, PL_SOA, true),
+    BIOIM_PLANE(resets, PE_I32, PC_ONE, PL_SOA, false),   /* the env's share of bioim_reset_count */
+    BIOIM_PLANE(hrk, PE_F64, PC_ONE, PL_SOA, true),
+    BIOIM_PLANE(pend, PE_I32, PC_ONE, PL_SOA, true),
+    BIOIM_PLANE(rkt, PE_F64, PC_ONE, PL_SOA, true),
+    BIOIM_PLANE(rkh, PE_F64, PC_ONE, PL_SOA, true),
+    BIOIM_PLANE(rka, PE_I32, PC_ONE, PL_SOA, true),
+    BIOIM_PLANE(ctl, PE_REAL, PC_NA1, PL_SOA, true),
+    BIOIM_PLANE(cur, PE_REAL, PC_NA1, PL_SOA, true),
+    BIOIM_PLANE(vnw, PE_REAL, PC_NM1, PL_SOA, true),
+    BIOIM_PLANE(rkev, PE_U64, PC_ONE, PL_SOA, false),     /* its share of bioim_eval_count / bioim_finished_count */
+    BIOIM_PLANE(cache, PE_REAL, PC_CACHE, PL_ROWS, true),
+    BIOIM_PLANE(cache_ok, PE_I32, PC_ONE, PL_SOA, true),
+};
+#undef BIOIM_PLANE
+constexpr int BIOIM_NPLANES = (int)(sizeof(g_state_planes) / sizeof(g_state_planes[0]));
+constexpr bool planes_cover_dstate() {   /* every pointer of DState is listed exactly once */
+    for (size_t k = 0; k < (size_t)BIOIM_NPLANES; ++k) {
+        int hits = 0;
+        for (const StatePlane &p : g_state_planes) hits += p.member == k * sizeof(void *) ? 1 : 0;
+        if (hits != 1) return false;
+    }
+    return true;
+}
+static_assert(sizeof(DState<double>) == BIOIM_NPLANES * sizeof(void *) && sizeof(DState<float>) == sizeof(DState<double>) &&
+                  planes_cover_dstate(),
+              "g_state_planes must list every plane of DState");
+
+static const StatePlane *find_plane(const char *name) {
+    for (const StatePlane &p : g_state_planes)
+        if (strcmp(p.name, name) == 0) return &p;
+    return nullptr;
+}
+static size_t plane_count(const bioim_handle_t *h, PlaneCount c) {
+    switch (c) {
+    case PC_NDOF: return (size_t)h->ndof;
+    case PC_NM1: return h->nmuscle ? (size_t)h->nmuscle : 1;
+    case PC_HIST: return (size_t)BIOIM_MAX_HORIZON * h->nact;
+    case PC_NACT: return (size_t)h->nact;
+    case PC_NA1: return h->nact ? (size_t)h->nact : 1;
+    case PC_CACHE: return (size_t)cache_dim(h);
+    default: return 1;
+    }
+}
+static size_t plane_elem_bytes(const bioim_handle_t *h, PlaneElem e) {
+    return e == PE_I32 ? 4 : e == PE_REAL ? (h->precision == 64 ? 8 : 4) : 8;
+}
+static size_t plane_bytes(const bioim_handle_t *h, const StatePlane &p) {
+    return plane_elem_bytes(h, p.elem) * plane_count(h, p.count) * (size_t)h->n;
+}
+static char *&plane_base(const bioim_handle_t *h, const StatePlane &p) {
+    return *reinterpret_cast<char **>(reinterpret_cast<char *>(h->dstate) + p.member);
+}
+
+/* one allocation for the whole record: the planes in table order, each
+ * rounded up to 256 bytes, zeroed; then the device model images */
+template <typename Real> static int alloc_state(bioim_handle_t *h) {
+    auto span = [h](const StatePlane &p) { return (plane_bytes(h, p) + 255) & ~(size_t)255; };
+    for (const StatePlane &p : g_state_planes) h->state_bytes += span(p);
+    HIPCHK(hipMalloc(&h->state_buf, h->state_bytes));
+    HIPCHK(hipMemsetAsync(h->state_buf, 0, h->state_bytes, h->stream));
+    h->dstate = new DState<Real>();
+    char *at = (char *)h->state_buf;
+    for (const StatePlane &p : g_state_planes) {
+        plane_base(h, p) = at;
+        at += span(p);
+    }
+    DModel<Real> *hm = new DModel<Real>();
+    convert_model<Real>(h->pack, *hm);
+    HIPCHK(hipMalloc(&h->model, sizeof(DModel<Real>)));
+    HIPCHK(hipMemcpyAsync(h->model, hm, sizeof(DModel<Real>), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    delete hm;
+    return h->ops.upload(h);
+}
+
+/* The flat state row (bioim_get_state's layout, documented in include/bioim.h
+ * at bioim_state_dim): the fields in order, each the first `count` rows of
+ * its plane.  This table is the only place the order is written: the row's
+ * length, row_offset and the gather / load kernel all walk it. */
+enum RowCount { RC_ONE, RC_NDOF, RC_NM, RC_HIST, RC_NACT };   /* values per env; RC_NM: nmuscle, not its plane's padded count */
+struct RowField {
+    const char *plane;
+    RowCount count;
+};
+static const RowField g_state_row[] = {
+    {"t", RC_ONE},   {"istep", RC_ONE}, {"has_last", RC_ONE}, {"old_px", RC_ONE}, {"done", RC_ONE},
+    {"q", RC_NDOF},  {"u", RC_NDOF},    {"act", RC_NM},       {"lce", RC_NM},
+    {"hist", RC_HIST},   /* [horizon][nact] = hh * nact + a, of the plane's BIOIM_MAX_HORIZON * nact rows */
+    {"last", RC_NACT},   {"hrk", RC_ONE},   {"ctl", RC_NACT},
+};
+constexpr int BIOIM_NROWFIELDS = (int)(sizeof(g_state_row) / sizeof(g_state_row[0]));
+
+static int row_count(const bioim_handle_t *h, RowCount c) {
+    switch (c) {
+    case RC_NDOF: return h->ndof;
+    case RC_NM: return h->nmuscle;
+    case RC_HIST: return h->horizon * h->nact;
+    case RC_NACT: return h->nact;
+    default: return 1;
+    }
+}
+/* where `field` starts in the row; null: past the last field, the row's length */
+static int row_offset(const bioim_handle_t *h, const char *field) {
+    int k = 0;
+    for (const RowField &f : g_state_row) {
+        if (field && strcmp(f.plane, field) == 0) break;
+        k += row_count(h, f.count);
+    }
+    return k;
+}
+
+/* the row table as the kernel takes it, by value */
+struct RowTable {
+    void *base[BIOIM_NROWFIELDS];
+    int32_t end[BIOIM_NROWFIELDS];    /* running sum of the counts: field f holds the row's values [end[f - 1], end[f]) */
+    int32_t elem[BIOIM_NROWFIELDS];   /* PlaneElem */
+    int32_t *pend, *cache_ok;         /* what a load clears */
+};
+static RowTable row_table(const bioim_handle_t *h) {
+    RowTable tb{};
+    int k = 0;
+    for (int f = 0; f < BIOIM_NROWFIELDS; ++f) {
+        const StatePlane &p = *find_plane(g_state_row[f].plane);
+        tb.base[f] = plane_base(h, p);
+        tb.end[f] = k += row_count(h, g_state_row[f].count);
+        tb.elem[f] = p.elem;
+    }
+    tb.pend = reinterpret_cast<int32_t *>(plane_base(h, *find_plane("pend")));
+    tb.cache_ok = reinterpret_cast<int32_t *>(plane_base(h, *find_plane("cache_ok")));
+    return tb;
+}
+
+/* one whole plane of the record, by name, copied to the host or from it;
+ * synchronizes both of the handle's streams.  `bytes` must be the plane's
+ * size; every argument check comes before the first device call. */
+static int plane_io(bioim_handle_t *h, const char *who, const char *name, void *host, size_t bytes, bool write) {
+    const StatePlane *pl = find_plane(name);
+    if (!pl) return fail(BIOIM_E_ARG, std::string(who) + ": no plane named '" + name + "'");
+    const size_t want = plane_bytes(h, *pl);
+    if (bytes != want)
+        return fail(BIOIM_E_ARG, std::string(who) + ": plane " + name + " holds " + std::to_string(want) +
+                                     " bytes, the buffer " + std::to_string(bytes));
+    if (want == 0) return 0;   /* the cache plane of a topology without a realize cache */
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipStreamSynchronize(h->side));   /* a group step may have run this handle on its side stream */
+    if (write) {
+        HIPCHK(hipMemcpy(plane_base(h, *pl), host, want, hipMemcpyHostToDevice));
+        /* flags set from outside count as live: the next push, RK or
+         * OsimModel launch clears them like a default launch's (launch_impl) */
+        if (strcmp(name, "cache_ok") == 0) h->cache_live = 1;
+    } else {
+        HIPCHK(hipMemcpy(host, plane_base(h, *pl), want, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+/* a plane of one value per env (V its element type) */
+template <typename V> static int read_plane(bioim_handle_t *h, const char *who, const char *name, std::vector<V> &out) {
+    out.resize((size_t)h->n);
+    return plane_io(h, who, name, out.data(), sizeof(V) * out.size(), false);
+}
 
 /* ================================================================ C-ABI */
 extern "C" {
@@ -4731,10 +4817,6 @@ int bioim_create(const bioim_modelpack_t *pack, int n_envs, int device, int prec
     }
     int rc = precision == 64 ? alloc_state<double>(h) : alloc_state<float>(h);
     if (rc) { bioim_destroy(h); return rc; }
-    if (!state_planes_match(h)) {   /* bioim_clone_envs would miss or misplace a plane */
-        bioim_destroy(h);
-        return fail(BIOIM_E_LAUNCH, "bioim_create: the state plane table does not reproduce state_layout");
-    }
     *out = h;
     return 0;
 }
@@ -4818,19 +4900,21 @@ static int build_reset_table(bioim_handle_t *h) {
         return done(fail(BIOIM_E_DEVICE, "build_reset_table: reset realize failed"));
     if ((rc = bioim_get_state(tmp, st.data())) != 0) return done(rc);
     if (nm > 0) {
+        const int lce = row_offset(tmp, "lce");
         for (int r = 0; r < nr; ++r)
             for (int m = 0; m < nm; ++m)   /* fiber_length[m] */
-                put(tab.data() + ((size_t)r * dim + m) * R, st[(size_t)r * sdim + 5 + 2 * nd + nm + m]);
+                put(tab.data() + ((size_t)r * dim + m) * R, st[(size_t)r * sdim + lce + m]);
     } else {
         /* torque models: M^-1 at each row's coordinates, column k = M^-1 e_k
          * (the inverse-dynamics kernel, BIOIM_ID_MULT_MINV: the realize's
          * mass matrix — at h = 0 no implicit contact or limit terms) */
         const size_t n = (size_t)nr * nd;
+        const int q0 = row_offset(tmp, "q");
         std::vector<unsigned char> q(n * nd * R), v(n * nd * R, 0), out(n * nd * R);
         for (int r = 0; r < nr; ++r)
             for (int k = 0; k < nd; ++k) {
                 const size_t s_ = (size_t)r * nd + k;   /* state: row r, unit vector e_k */
-                for (int d = 0; d < nd; ++d) put(q.data() + (s_ * nd + d) * R, st[(size_t)r * sdim + 5 + d]);
+                for (int d = 0; d < nd; ++d) put(q.data() + (s_ * nd + d) * R, st[(size_t)r * sdim + q0 + d]);
                 put(v.data() + (s_ * nd + k) * R, 1.0);
             }
         if (hipMalloc(&d_q, q.size()) != hipSuccess || hipMalloc(&d_v, v.size()) != hipSuccess ||
@@ -4851,11 +4935,8 @@ static int build_reset_table(bioim_handle_t *h) {
     for (int r = 0; r < nr; ++r)
         memcpy(tab.data() + ((size_t)r * dim + head) * R, obs.data() + (size_t)r * od * R, (size_t)od * R);
     if (cdim > 0) {   /* the reset realize's cache rows (DState::cache, [nr][cdim]) */
-        const DState<double> &ts = *reinterpret_cast<const DState<double> *>(tmp->dstate);
-        const size_t cb = (size_t)nr * cdim * R;
-        std::vector<unsigned char> crow(cb);
-        if (hipMemcpy(crow.data(), ts.cache, cb, hipMemcpyDeviceToHost) != hipSuccess)
-            return done(fail(BIOIM_E_DEVICE, "build_reset_table: cache rows failed"));
+        std::vector<unsigned char> crow((size_t)nr * cdim * R);
+        if ((rc = plane_io(tmp, "build_reset_table", "cache", crow.data(), crow.size(), false)) != 0) return done(rc);
         for (int r = 0; r < nr; ++r)
             memcpy(tab.data() + ((size_t)r * dim + head + od) * R, crow.data() + (size_t)r * cdim * R, (size_t)cdim * R);
     }
@@ -4935,13 +5016,8 @@ int bioim_set_active_mask(bioim_handle_t *h, const uint8_t *active) {
 
 int bioim_pending_count(bioim_handle_t *h) {
     if (!h) return fail(BIOIM_E_ARG, "null handle");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipStreamSynchronize(h->side));   /* a group step may have run this handle on its side stream */
-    std::vector<int32_t> p(h->n);
-    const int32_t *dp = h->precision == 64 ? reinterpret_cast<DState<double> *>(h->dstate)->pend
-                                           : reinterpret_cast<DState<float> *>(h->dstate)->pend;
-    HIPCHK(hipMemcpy(p.data(), dp, sizeof(int32_t) * h->n, hipMemcpyDeviceToHost));
+    std::vector<int32_t> p;
+    if (const int rc = read_plane(h, "bioim_pending_count", "pend", p)) return rc;
     int c = 0;
     for (int32_t v : p) c += v != 0;
     return c;
@@ -5117,13 +5193,7 @@ int bioim_set_env_offset(bioim_handle_t *h, int offset) {
 
 int bioim_state_dim(const bioim_handle_t *h) {
     if (!h) return fail(BIOIM_E_ARG, "null handle");
-    return 5 + 2 * h->ndof + 2 * h->nmuscle + h->horizon * h->nact + h->nact + 1 + h->nact;
-}
-
-int bioim_get_state(bioim_handle_t *h, double *host_state) {
-    if (!h || !host_state) return fail(BIOIM_E_ARG, "bioim_get_state: bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    return h->precision == 64 ? xfer_state<double>(h, host_state, nullptr) : xfer_state<float>(h, host_state, nullptr);
+    return row_offset(h, nullptr);
 }
 
 /* bioim_copy_state: the flat state rows (bioim_get_state's layout) gathered
@@ -5133,141 +5203,53 @@ int bioim_get_state(bioim_handle_t *h, double *host_state) {
  * the same for a list of envs, bioim_load_state writes such rows back and
  * bioim_clone_envs copies whole envs.
  *
- * The kernels below (rows gather, rows load, env clone) take
- * the model's sizes as run-time arguments: no topology template, this unit
- * alone holds them.  Each reads its env ids from a device list and skips an
- * id outside [0, N) instead of using it.
+ * The kernels below (rows gather / load, env clone) take the
+ * record as a table argument: no topology template, this unit alone holds
+ * them.  Each reads its env ids from a device list and skips an id outside
+ * [0, N) instead of using it.
  *
- * state_rows_kernel: row r of out = the flat state row of env ids[r] (ids
- * null: env r), n rows.  state_load_kernel: the inverse, with xfer_state's
- * conversions; the thread of a row's first value also marks the env as at a
- * step boundary (pend) and its realize-cache row as stale (cache_ok). */
+ * state_rows_kernel walks the row table (RowTable): row r of `rows` is the
+ * flat state row of env ids[r] (ids null: env r), n rows.  Gather: values to
+ * double.  LOAD: the inverse, values to the plane's element type (reals to
+ * Real, istep / has_last / done through int32_t, t and hrk stay double); the
+ * thread of a row's first value also marks the env as at a step boundary
+ * (pend) and its realize-cache row as stale (cache_ok). */
 extern "C++" {
-template <typename Real>
-__global__ void state_rows_kernel(DState<Real> st, int n_envs, const int32_t *ids, int n, int nd, int nm, int na, int H,
-                                  int dim, double *out) {
+template <typename V, bool LOAD> DEV void row_value(void *base, size_t j, size_t count, double &v) {
+    V *p = reinterpret_cast<V *>(base);
+    if constexpr (LOAD) GAT(p, j, count) = (V)v;
+    else v = (double)GAT(p, j, count);
+}
+
+template <typename Real, bool LOAD>
+__global__ void state_rows_kernel(RowTable tb, int n_envs, const int32_t *ids, int n, double *rows) {
+    const int dim = tb.end[BIOIM_NROWFIELDS - 1];
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, total = (size_t)n * dim;
     if (i >= total) return;
-    const int r = (int)(i / dim);
-    int k = (int)(i % dim);
+    const int r = (int)(i / dim), k = (int)(i % dim);
     const int e = ids ? GAT(ids, r, n) : r;
     if (e < 0 || e >= n_envs) return;
     const size_t N = (size_t)n_envs;
-    double v = 0;
-    if (k < 5) {
-        v = k == 0 ? GAT(st.t, e, N) : k == 1 ? (double)GAT(st.istep, e, N) : k == 2 ? (double)GAT(st.has_last, e, N)
-          : k == 3 ? (double)GAT(st.old_px, e, N) : (double)GAT(st.done, e, N);
-    } else if ((k -= 5) < nd) v = GAT(st.q, k * N + e, nd * N);
-    else if ((k -= nd) < nd) v = GAT(st.u, k * N + e, nd * N);
-    else if ((k -= nd) < nm) v = GAT(st.act, k * N + e, nm * N);
-    else if ((k -= nm) < nm) v = GAT(st.lce, k * N + e, nm * N);
-    else if ((k -= nm) < H * na) v = GAT(st.hist, k * N + e, (size_t)H * na * N);   /* [hh][a] = hh * na + a */
-    else if ((k -= H * na) < na) v = GAT(st.last, k * N + e, na * N);
-    else if ((k -= na) == 0) v = GAT(st.hrk, e, N);
-    else v = GAT(st.ctl, (k - 1) * N + e, na * N);
-    GAT(out, i, total) = v;
-}
-
-template <typename Real>
-__global__ void state_load_kernel(DState<Real> st, int n_envs, const int32_t *ids, int n, int nd, int nm, int na, int H,
-                                  int dim, const double *rows) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, total = (size_t)n * dim;
-    if (i >= total) return;
-    const int r = (int)(i / dim);
-    int k = (int)(i % dim);
-    const int e = ids ? GAT(ids, r, n) : r;
-    if (e < 0 || e >= n_envs) return;
-    const size_t N = (size_t)n_envs;
-    const double v = GAT(rows, i, total);
-    if (k == 0) {
-        GAT(st.t, e, N) = v;
-        GAT(st.pend, e, N) = 0;       /* a state set from outside is at a step boundary */
-        GAT(st.cache_ok, e, N) = 0;   /* the realize cache belongs to the state it was formed at */
-    } else if (k == 1) GAT(st.istep, e, N) = (int32_t)v;
-    else if (k == 2) GAT(st.has_last, e, N) = (int32_t)v;
-    else if (k == 3) GAT(st.old_px, e, N) = (Real)v;
-    else if (k == 4) GAT(st.done, e, N) = (int32_t)v;
-    else if ((k -= 5) < nd) GAT(st.q, k * N + e, nd * N) = (Real)v;
-    else if ((k -= nd) < nd) GAT(st.u, k * N + e, nd * N) = (Real)v;
-    else if ((k -= nd) < nm) GAT(st.act, k * N + e, nm * N) = (Real)v;
-    else if ((k -= nm) < nm) GAT(st.lce, k * N + e, nm * N) = (Real)v;
-    else if ((k -= nm) < H * na) GAT(st.hist, k * N + e, (size_t)H * na * N) = (Real)v;
-    else if ((k -= H * na) < na) GAT(st.last, k * N + e, na * N) = (Real)v;
-    else if ((k -= na) == 0) GAT(st.hrk, e, N) = v;
-    else GAT(st.ctl, (k - 1) * N + e, na * N) = (Real)v;
-}
-
-/* The per-env record: every plane of DState, in state_layout's order.  The
- * clone launch walks this table, and bioim_create checks it against the
- * pointers state_layout produced (state_planes_match), so a plane added to
- * the state cannot be left out of it silently. */
-enum PlaneElem { PE_REAL, PE_F64, PE_I32, PE_U64 };
-enum PlaneCount { PC_ONE, PC_NDOF, PC_NM1, PC_HIST, PC_NACT, PC_NA1, PC_CACHE };   /* elements per env */
-enum PlaneLayout { PL_SOA, PL_ROWS };   /* [count][N], env fastest | [N][count], row-major per env */
-struct StatePlane {
-    const char *name;
-    size_t member;   /* offset of the plane's pointer in DState (the same for both precisions) */
-    PlaneElem elem;
-    PlaneCount count;
-    PlaneLayout layout;
-    bool cloned;
-};
-#define BIOIM_PLANE(m, elem, count, layout, cloned) {#m, __builtin_offsetof(DState<double>, m), elem, count, layout, cloned}
-static const StatePlane g_state_planes[] = {
-    BIOIM_PLANE(q, PE_REAL, PC_NDOF, PL_SOA, true),
-    BIOIM_PLANE(u, PE_REAL, PC_NDOF, PL_SOA, true),
-    BIOIM_PLANE(act, PE_REAL, PC_NM1, PL_SOA, true),
-    BIOIM_PLANE(lce, PE_REAL, PC_NM1, PL_SOA, true),
-    BIOIM_PLANE(hist, PE_REAL, PC_HIST, PL_SOA, true),
-    BIOIM_PLANE(last, PE_REAL, PC_NACT, PL_SOA, true),
-    BIOIM_PLANE(old_px, PE_REAL, PC_ONE, PL_SOA, true),
-    BIOIM_PLANE(t, PE_F64, PC_ONE, PL_SOA, true),
-    BIOIM_PLANE(istep, PE_I32, PC_ONE, PL_SOA, true),
-    BIOIM_PLANE(has_last, PE_I32, PC_ONE, PL_SOA, true),
-    BIOIM_PLANE(done, PE_I32, PC_ONE, PL_SOA, true),
-    BIOIM_PLANE(resets, PE_I32, PC_ONE, PL_SOA, false),   /* the env's share of bioim_reset_count */
-    BIOIM_PLANE(hrk, PE_F64, PC_ONE, PL_SOA, true),
-    BIOIM_PLANE(pend, PE_I32, PC_ONE, PL_SOA, true),
-    BIOIM_PLANE(rkt, PE_F64, PC_ONE, PL_SOA, true),
-    BIOIM_PLANE(rkh, PE_F64, PC_ONE, PL_SOA, true),
-    BIOIM_PLANE(rka, PE_I32, PC_ONE, PL_SOA, true),
-    BIOIM_PLANE(ctl, PE_REAL, PC_NA1, PL_SOA, true),
-    BIOIM_PLANE(cur, PE_REAL, PC_NA1, PL_SOA, true),
-    BIOIM_PLANE(vnw, PE_REAL, PC_NM1, PL_SOA, true),
-    BIOIM_PLANE(rkev, PE_U64, PC_ONE, PL_SOA, false),     /* its share of bioim_eval_count / bioim_finished_count */
-    BIOIM_PLANE(cache, PE_REAL, PC_CACHE, PL_ROWS, true),
-    BIOIM_PLANE(cache_ok, PE_I32, PC_ONE, PL_SOA, true),
-};
-#undef BIOIM_PLANE
-constexpr int BIOIM_NPLANES = (int)(sizeof(g_state_planes) / sizeof(g_state_planes[0]));
-static_assert(sizeof(DState<double>) == BIOIM_NPLANES * sizeof(void *) && sizeof(DState<float>) == sizeof(DState<double>),
-              "g_state_planes must list every plane of DState");
-
-static size_t plane_count(const bioim_handle_t *h, PlaneCount c) {
-    switch (c) {
-    case PC_NDOF: return (size_t)h->ndof;
-    case PC_NM1: return h->nmuscle ? (size_t)h->nmuscle : 1;
-    case PC_HIST: return (size_t)BIOIM_MAX_HORIZON * h->nact;
-    case PC_NACT: return (size_t)h->nact;
-    case PC_NA1: return h->nact ? (size_t)h->nact : 1;
-    case PC_CACHE: return (size_t)cache_dim(h);
-    default: return 1;
+    double v = LOAD ? GAT(rows, i, total) : 0;
+    int first = 0;
+#pragma unroll
+    for (int f = 0; f < BIOIM_NROWFIELDS; ++f) {
+        if (k >= first && k < tb.end[f]) {
+            const size_t j = (size_t)(k - first) * N + e, count = (size_t)(tb.end[f] - first) * N;
+            if (tb.elem[f] == PE_REAL) row_value<Real, LOAD>(tb.base[f], j, count, v);
+            else if (tb.elem[f] == PE_I32) row_value<int32_t, LOAD>(tb.base[f], j, count, v);
+            else row_value<double, LOAD>(tb.base[f], j, count, v);
+        }
+        first = tb.end[f];
     }
-}
-static size_t plane_elem_bytes(const bioim_handle_t *h, PlaneElem e) {
-    return e == PE_I32 ? 4 : e == PE_REAL ? (h->precision == 64 ? 8 : 4) : 8;
-}
-static char *plane_base(const bioim_handle_t *h, const StatePlane &p) {
-    return *reinterpret_cast<char *const *>(reinterpret_cast<const char *>(h->dstate) + p.member);
-}
-/* the table reproduces state_layout: same order, sizes and 256-byte rounding */
-static bool state_planes_match(const bioim_handle_t *h) {
-    size_t off = 0;
-    for (const StatePlane &p : g_state_planes) {
-        if (plane_base(h, p) != (char *)h->state_buf + off) return false;
-        off += (plane_elem_bytes(h, p.elem) * plane_count(h, p.count) * (size_t)h->n + 255) & ~(size_t)255;
+    if constexpr (LOAD) {
+        if (k == 0) {
+            GAT(tb.pend, e, N) = 0;       /* a state set from outside is at a step boundary */
+            GAT(tb.cache_ok, e, N) = 0;   /* the realize cache belongs to the state it was formed at */
+        }
+    } else {
+        GAT(rows, i, total) = v;
     }
-    return off == h->state_bytes;
 }
 
 /* clone_envs_kernel's view of the cloned planes.  SoA planes are copied as
@@ -5319,36 +5301,23 @@ __global__ void clone_envs_kernel(ClonePlanes pl, int n_envs, const int32_t *src
 }
 }  // extern "C++"
 
-static int state_rows_launch(bioim_handle_t *h, const int32_t *env_ids, int n, const double *rows_in, double *rows_out) {
+/* n flat rows between the device buffer `rows` and the envs env_ids (null:
+ * envs 0 .. n - 1), on the handle's stream */
+static int state_rows_launch(bioim_handle_t *h, const int32_t *env_ids, int n, double *rows, bool load) {
     HIPCHK(hipSetDevice(h->device));
-    const int dim = bioim_state_dim(h);
-    const size_t total = (size_t)n * dim;
+    const size_t total = (size_t)n * bioim_state_dim(h);
     const int bs = 256;
-    const dim3 g((unsigned)((total + bs - 1) / bs)), b(bs);
-    if (h->precision == 64) {
-        const DState<double> &st = *reinterpret_cast<DState<double> *>(h->dstate);
-        if (rows_out)
-            hipLaunchKernelGGL(state_rows_kernel<double>, g, b, 0, h->stream, st, h->n, env_ids, n, h->ndof, h->nmuscle,
-                               h->nact, h->horizon, dim, rows_out);
-        else
-            hipLaunchKernelGGL(state_load_kernel<double>, g, b, 0, h->stream, st, h->n, env_ids, n, h->ndof, h->nmuscle,
-                               h->nact, h->horizon, dim, rows_in);
-    } else {
-        const DState<float> &st = *reinterpret_cast<DState<float> *>(h->dstate);
-        if (rows_out)
-            hipLaunchKernelGGL(state_rows_kernel<float>, g, b, 0, h->stream, st, h->n, env_ids, n, h->ndof, h->nmuscle,
-                               h->nact, h->horizon, dim, rows_out);
-        else
-            hipLaunchKernelGGL(state_load_kernel<float>, g, b, 0, h->stream, st, h->n, env_ids, n, h->ndof, h->nmuscle,
-                               h->nact, h->horizon, dim, rows_in);
-    }
+    auto kernel = h->precision == 64 ? (load ? state_rows_kernel<double, true> : state_rows_kernel<double, false>)
+                                     : (load ? state_rows_kernel<float, true> : state_rows_kernel<float, false>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((total + bs - 1) / bs)), dim3(bs), 0, h->stream, row_table(h), h->n, env_ids,
+                       n, rows);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
 int bioim_copy_state(bioim_handle_t *h, void *device_out) {
     if (!h || !device_out) return fail(BIOIM_E_ARG, "bioim_copy_state: bad arguments");
-    return state_rows_launch(h, nullptr, h->n, nullptr, reinterpret_cast<double *>(device_out));
+    return state_rows_launch(h, nullptr, h->n, reinterpret_cast<double *>(device_out), false);
 }
 
 int bioim_copy_state_rows(bioim_handle_t *h, const int32_t *env_ids, int n, void *device_out) {
@@ -5356,7 +5325,7 @@ int bioim_copy_state_rows(bioim_handle_t *h, const int32_t *env_ids, int n, void
     if (!device_out) return fail(BIOIM_E_ARG, "bioim_copy_state_rows: null output buffer");
     if (env_ids && (n <= 0 || n > h->n))
         return fail(BIOIM_E_ARG, "bioim_copy_state_rows: n must lie in [1, n_envs] with an id list");
-    return state_rows_launch(h, env_ids, env_ids ? n : h->n, nullptr, reinterpret_cast<double *>(device_out));
+    return state_rows_launch(h, env_ids, env_ids ? n : h->n, reinterpret_cast<double *>(device_out), false);
 }
 
 int bioim_load_state(bioim_handle_t *h, const int32_t *env_ids, int n, const void *device_rows) {
@@ -5364,7 +5333,42 @@ int bioim_load_state(bioim_handle_t *h, const int32_t *env_ids, int n, const voi
     if (!device_rows) return fail(BIOIM_E_ARG, "bioim_load_state: null rows buffer");
     if (env_ids && (n <= 0 || n > h->n))
         return fail(BIOIM_E_ARG, "bioim_load_state: n must lie in [1, n_envs] with an id list");
-    return state_rows_launch(h, env_ids, env_ids ? n : h->n, reinterpret_cast<const double *>(device_rows), nullptr);
+    return state_rows_launch(h, env_ids, env_ids ? n : h->n, (double *)device_rows, true);   /* a load only reads them */
+}
+
+/* bioim_get_state / bioim_set_state: every env's row between the host and
+ * the record, through a temporary device buffer and the row kernel;
+ * synchronous, on both of the handle's streams */
+static int host_rows(bioim_handle_t *h, double *host, bool load) {
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->side));
+    const size_t bytes = sizeof(double) * (size_t)h->n * bioim_state_dim(h);
+    double *dev = nullptr;
+    HIPCHK(hipMalloc(&dev, bytes));
+    hipError_t e = load ? hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, h->stream) : hipSuccess;
+    const int rc = e == hipSuccess ? state_rows_launch(h, nullptr, h->n, dev, load) : 0;
+    if (e == hipSuccess && !rc && !load) e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, h->stream);
+    const hipError_t es = hipStreamSynchronize(h->stream);
+    hipFree(dev);
+    if (rc) return rc;
+    HIPCHK(e);
+    HIPCHK(es);
+    return 0;
+}
+
+int bioim_get_state(bioim_handle_t *h, double *host_state) {
+    if (!h || !host_state) return fail(BIOIM_E_ARG, "bioim_get_state: bad arguments");
+    const int np = bioim_pending_count(h);
+    if (np < 0) return np;
+    if (np > 0)   /* mid-step: t is the step's end time but q/u/act/lce an accepted RK point */
+        return fail(BIOIM_E_ARG, "bioim_get_state: envs are suspended mid-step by the RK budget "
+                                 "(step until bioim_pending_count() is 0)");
+    return host_rows(h, host_state, false);
+}
+
+int bioim_set_state(bioim_handle_t *h, const double *host_state) {
+    if (!h || !host_state) return fail(BIOIM_E_ARG, "bioim_set_state: bad arguments");
+    return host_rows(h, const_cast<double *>(host_state), true);
 }
 
 int bioim_clone_envs(bioim_handle_t *h, const int32_t *src_ids, const int32_t *dst_ids, int n) {
@@ -5399,31 +5403,11 @@ int bioim_clone_envs(bioim_handle_t *h, const int32_t *src_ids, const int32_t *d
     return 0;
 }
 
-int bioim_set_state(bioim_handle_t *h, const double *host_state) {
-    if (!h || !host_state) return fail(BIOIM_E_ARG, "bioim_set_state: bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    return h->precision == 64 ? xfer_state<double>(h, nullptr, host_state) : xfer_state<float>(h, nullptr, host_state);
-}
-
-/* one per-env plane of the device state (a DState member; the pointer
- * layout is the same for both precisions), copied to the host — the
- * counters read that plane alone, not the whole state (round 6: with the
- * realize cache the state is ~10 MB at 4096 envs) */
-extern "C++" template <typename V> static int read_plane(bioim_handle_t *h, V *DState<double>::*member, std::vector<V> &out) {
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipStreamSynchronize(h->side));
-    const DState<double> &st = *reinterpret_cast<const DState<double> *>(h->dstate);
-    out.resize((size_t)h->n);
-    HIPCHK(hipMemcpy(out.data(), st.*member, sizeof(V) * (size_t)h->n, hipMemcpyDeviceToHost));
-    return 0;
-}
-
 /* total resets (explicit + in-kernel auto-resets) over the handle's envs */
 int bioim_reset_count(bioim_handle_t *h, uint64_t *total) {
     if (!h || !total) return fail(BIOIM_E_ARG, "bioim_reset_count: bad arguments");
     std::vector<int32_t> r;
-    if (const int rc = read_plane<int32_t>(h, &DState<double>::resets, r)) return rc;
+    if (const int rc = read_plane(h, "bioim_reset_count", "resets", r)) return rc;
     uint64_t sum = 0;
     for (int e = 0; e < h->n; ++e) sum += (uint32_t)r[e];
     *total = sum;
@@ -5434,7 +5418,7 @@ int bioim_reset_count(bioim_handle_t *h, uint64_t *total) {
 static int rk_counter(bioim_handle_t *h, uint64_t *total, bool fin, const char *who) {
     if (!h || !total) return fail(BIOIM_E_ARG, std::string(who) + ": bad arguments");
     std::vector<uint64_t> r;
-    if (const int rc = read_plane<uint64_t>(h, &DState<double>::rkev, r)) return rc;
+    if (const int rc = read_plane(h, who, "rkev", r)) return rc;
     uint64_t sum = 0;
     for (int e = 0; e < h->n; ++e) sum += (uint32_t)(fin ? r[e] >> 32 : r[e]);
     *total = sum;
@@ -5452,52 +5436,16 @@ int bioim_finished_count(bioim_handle_t *h, uint64_t *total) {
 
 int bioim_set_rk_counters(bioim_handle_t *h, uint32_t evals, uint32_t finished) {
     if (!h) return fail(BIOIM_E_ARG, "bioim_set_rk_counters: null handle");
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipStreamSynchronize(h->side));
-    std::vector<char> buf(h->state_bytes);
-    HIPCHK(hipMemcpy(buf.data(), h->state_buf, h->state_bytes, hipMemcpyDeviceToHost));
-    const uint64_t v = ((uint64_t)finished << 32) | evals;
-    if (h->precision == 64) {
-        DState<double> hs;
-        state_layout<double>(h, buf.data(), &hs);
-        for (int e = 0; e < h->n; ++e) hs.rkev[e] = v;
-    } else {
-        DState<float> hs;
-        state_layout<float>(h, buf.data(), &hs);
-        for (int e = 0; e < h->n; ++e) hs.rkev[e] = v;
-    }
-    HIPCHK(hipMemcpy(h->state_buf, buf.data(), h->state_bytes, hipMemcpyHostToDevice));
-    return 0;
+    std::vector<uint64_t> v((size_t)h->n, ((uint64_t)finished << 32) | evals);
+    return plane_io(h, "bioim_set_rk_counters", "rkev", v.data(), sizeof(uint64_t) * v.size(), true);
 }
 
 /* debug / tests: one whole plane of the per-env record (g_state_planes, by
- * name) copied to the host, or from it.  Every argument check comes before
- * the first device call. */
+ * name) copied to the host, or from it (plane_io). */
 int bioim_debug_plane(bioim_handle_t *h, const char *name, void *host, size_t bytes, int write) {
     if (!h) return fail(BIOIM_E_ARG, "bioim_debug_plane: null handle");
     if (!name || !host) return fail(BIOIM_E_ARG, "bioim_debug_plane: null plane name or host buffer");
-    const StatePlane *pl = nullptr;
-    for (const StatePlane &p : g_state_planes)
-        if (strcmp(p.name, name) == 0) pl = &p;
-    if (!pl) return fail(BIOIM_E_ARG, std::string("bioim_debug_plane: no plane named '") + name + "'");
-    const size_t want = plane_elem_bytes(h, pl->elem) * plane_count(h, pl->count) * (size_t)h->n;
-    if (bytes != want)
-        return fail(BIOIM_E_ARG, std::string("bioim_debug_plane: plane ") + name + " holds " + std::to_string(want) +
-                                     " bytes, the buffer " + std::to_string(bytes));
-    if (want == 0) return 0;   /* the cache plane of a topology without a realize cache */
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipStreamSynchronize(h->side));
-    if (write) {
-        HIPCHK(hipMemcpy(plane_base(h, *pl), host, want, hipMemcpyHostToDevice));
-        /* flags set from outside count as live: the next push, RK or
-         * OsimModel launch clears them like a default launch's (launch_impl) */
-        if (strcmp(name, "cache_ok") == 0) h->cache_live = 1;
-    } else {
-        HIPCHK(hipMemcpy(host, plane_base(h, *pl), want, hipMemcpyDeviceToHost));
-    }
-    return 0;
+    return plane_io(h, "bioim_debug_plane", name, host, bytes, write != 0);
 }
 
 int bioim_query(const bioim_handle_t *h, int32_t *out) {

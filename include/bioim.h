@@ -38,11 +38,7 @@
  *     topology has no compiled kernel is an error (there is no CPU fallback).
  *
  * Flat per-env state (bioim_get_state/set_state, doubles), matching the
- * oracle's layout: [t, istep, has_last, old_pelvis_x, done, q[ndof], u[ndof],
- * activation[nmuscle], fiber_length[nmuscle], hist[horizon][nact],
- * last_action[nact], rk_step_size, controls[nact]] — controls are the held
- * actuator controls (the PrescribedController's Constant functions, set by
- * each step's actuate and kept through resets).
+ * oracle's layout: the field order is given at bioim_state_dim below.
  */
 #ifndef BIOIM_H
 #define BIOIM_H
@@ -207,7 +203,31 @@ int bioim_osim(bioim_handle_t *h, int op, const int32_t *env_ids, int n, const v
  * bit-identical to an unsharded one. */
 int bioim_set_env_offset(bioim_handle_t *h, int offset);
 
-/* Host-side state transfer (synchronous). */
+/* Host-side state transfer (synchronous).
+ *
+ * The flat state row, state_dim doubles per env, holds these fields in this
+ * order (the oracle's layout):
+ *
+ *   field     values          meaning
+ *   t         1               time
+ *   istep     1               step index (an int32 in the record)
+ *   has_last  1               a last action exists (int32)
+ *   old_px    1               pelvis x at the last step
+ *   done      1               (int32)
+ *   q         ndof            coordinates
+ *   u         ndof            speeds
+ *   act       nmuscle         activations
+ *   lce       nmuscle         fiber lengths
+ *   hist      horizon * nact  action history, index hh * nact + a
+ *   last      nact            last action
+ *   hrk       1               RK-Merson step size carried to the next step
+ *   ctl       nact            held actuator controls (the PrescribedController's
+ *                             Constant functions, set by each step's actuate
+ *                             and kept through resets)
+ *
+ * state_dim = 5 + 2 ndof + 2 nmuscle + horizon nact + nact + 1 + nact.
+ * Values are stored in the handle's precision, t and hrk always as doubles;
+ * bioim_set_state / bioim_load_state truncate the int32 fields. */
 int bioim_state_dim(const bioim_handle_t *h);
 int bioim_get_state(bioim_handle_t *h, double *host_state /* [N][state_dim] */);
 int bioim_set_state(bioim_handle_t *h, const double *host_state);

@@ -162,3 +162,27 @@ def test_outdated_pack_version_is_refused():
     for blob in (bytes(b), bytes(b[:-8 * 8])):       # same size, and a smaller (older) layout
         with pytest.raises(ValueError, match='version 2'):
             pack_from_bytes(blob)
+
+
+def test_state_row_slices_tile_the_row():
+    """packdef.state_row_slices over every shipped pack: the fields come in
+    the order include/bioim.h documents at bioim_state_dim, tile [0, dim)
+    without gap or overlap and add up to the documented length."""
+    from bioimitation.registry import RECIPES
+    order = ('t', 'istep', 'has_last', 'old_px', 'done', 'q', 'u', 'act', 'lce', 'hist', 'last', 'hrk', 'ctl')
+    assert P.STATE_ROW_FIELDS == order
+    import re
+    txt = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'bioim.h')).read()
+    doc = txt[txt.index('The flat state row, state_dim doubles'):txt.index('int bioim_state_dim(')]
+    assert tuple(re.findall(r'^ \*   (\w+) +\S', doc, flags=re.M)) == ('field',) + order   # the header's table
+    for env_id in sorted(RECIPES):
+        pk = load_pack(env_id)
+        nd, nm, na, H = pk.ndof, pk.nmuscle, pk.nact, pk.horizon
+        sl, dim = P.state_row_slices(nd, nm, na, H)
+        assert tuple(sl) == order, env_id
+        want = {'q': nd, 'u': nd, 'act': nm, 'lce': nm, 'hist': H * na, 'last': na, 'ctl': na}
+        k = 0
+        for f in order:
+            assert (sl[f].start, sl[f].stop, sl[f].step) == (k, k + want.get(f, 1), None), (env_id, f)
+            k = sl[f].stop
+        assert k == dim == 5 + 2 * nd + 2 * nm + H * na + na + 1 + na, env_id
