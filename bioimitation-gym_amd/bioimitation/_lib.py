@@ -20,7 +20,8 @@ EXPORTS = ['bioim_create', 'bioim_destroy', 'bioim_reset', 'bioim_step', 'bioim_
            'bioim_last_error', 'bioim_modelpack_size', 'bioim_build_id', 'bioim_reset_count', 'bioim_set_final_obs', 'bioim_set_integrator', 'bioim_force_report_dim', 'bioim_set_force_report',
            'bioim_set_rk_budget', 'bioim_pending_count', 'bioim_set_active_mask', 'bioim_osim', 'bioim_osim_report_dim', 'bioim_eval_count', 'bioim_set_state_storage',
            'bioim_finished_count', 'bioim_set_rk_counters', 'bioim_copy_state', 'bioim_copy_state_rows', 'bioim_load_state',
-           'bioim_clone_envs', 'bioim_debug_plane', 'bioim_rollout', 'bioim_rollout_fused']
+           'bioim_clone_envs', 'bioim_debug_plane', 'bioim_rollout', 'bioim_rollout_fused', 'bioim_rollout_group',
+           'bioim_rollout_group_fused']
 
 _lib = None
 
@@ -82,6 +83,8 @@ def load():
         'bioim_clone_envs': (C.c_int, [vp, vp, vp, C.c_int]),
         'bioim_rollout': (C.c_int, [vp, vp, C.c_int, C.c_int64, vp, vp, vp, vp, vp, C.c_int]),
         'bioim_rollout_fused': (C.c_int, [vp]),
+        'bioim_rollout_group': (C.c_int, [C.POINTER(vp), C.c_int, vp, C.c_int, C.c_int64, vp, vp, vp, vp, vp, C.c_int]),
+        'bioim_rollout_group_fused': (C.c_int, [vp]),
         'bioim_set_state_storage': (C.c_int, [vp, vp, C.c_int, vp]),
         'bioim_debug_plane': (C.c_int, [vp, C.c_char_p, vp, C.c_size_t, C.c_int]),
     }

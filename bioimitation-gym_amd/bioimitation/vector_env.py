@@ -48,6 +48,58 @@ def check_env_mask(mask, num_envs, device):
         raise ValueError('env mask must be contiguous')
 
 
+def _rollout_buffers(env, actions, steps, obs, info, stop_with_auto_reset, out, zero):
+    """``rollout()``'s argument checks for a batch ``env`` (its num_envs,
+    action_dim, obs_dim, info_dim, dtype and device): the actions as the
+    kernel reads them, T, the action stride between steps in elements, and
+    the sequence buffers by name — the caller's ``out`` entries, checked, or
+    new tensors (zero-filled with ``zero``)."""
+    import torch
+    if obs not in ('last', 'all', None):
+        raise ValueError(f"rollout: obs must be 'last', 'all' or None, got {obs!r}")
+    if not isinstance(actions, torch.Tensor):
+        raise ValueError('rollout: actions must be a torch tensor')
+    n, na = env.num_envs, env.action_dim
+    if actions.dim() == 2:
+        if steps is None:
+            raise ValueError('rollout: (N, A) actions need steps=T')
+        T, stride = int(steps), 0
+        want = (n, na)
+    else:
+        T = int(actions.shape[0]) if actions.dim() == 3 else 0
+        if steps is not None and int(steps) != T:
+            raise ValueError(f'rollout: steps={steps} but actions hold {T} steps')
+        stride = n * na
+        want = (T, n, na)
+    if T <= 0 or tuple(actions.shape) != want:
+        raise ValueError(f'rollout: actions must have shape (T, {n}, {na}) or ({n}, {na}) with steps=T >= 1, '
+                         f'got {tuple(actions.shape)}')
+    if stop_with_auto_reset:
+        raise ValueError('rollout: stop_at_done needs auto-reset off')
+    a = actions
+    if a.dtype != env.dtype or a.device != env.device or not a.is_contiguous():
+        a = a.to(device=env.device, dtype=env.dtype).contiguous()
+    out = dict(out or {})
+    unknown = set(out) - {'obs', 'reward', 'done', 'info'}
+    if unknown:
+        raise ValueError(f'rollout: unknown out buffers {sorted(unknown)}')
+    shapes = {'reward': ((T, n), env.dtype), 'done': ((T, n), torch.uint8)}
+    if obs == 'all':
+        shapes['obs'] = ((T, n, env.obs_dim), env.dtype)
+    if info:
+        shapes['info'] = ((T, n, env.info_dim), env.dtype)
+    for k in out:
+        if k not in shapes:
+            raise ValueError(f"rollout: out['{k}'] given but not asked for (obs={obs!r}, info={info})")
+    buf = {}
+    for k, (shape, dtype) in shapes.items():
+        if k in out:
+            buf[k] = VectorEnv._check_seq(env, out[k], shape, dtype, f"out['{k}']")
+        else:
+            buf[k] = (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=env.device)
+    return a, T, stride, buf
+
+
 class VectorEnv:
     def __init__(self, env_id: str, num_envs: int, config: dict = None, device: int = 0, precision: int = 64,
                  seed: int = 0, auto_reset: bool = False, env_offset: int = 0):
@@ -350,49 +402,8 @@ class VectorEnv:
         'info' (T, N, I); contiguous, of the env's dtype, on its device.
 
         Returns (obs, reward (T, N), done (T, N) uint8, info or None)."""
-        import torch
-        if obs not in ('last', 'all', None):
-            raise ValueError(f"rollout: obs must be 'last', 'all' or None, got {obs!r}")
-        if not isinstance(actions, torch.Tensor):
-            raise ValueError('rollout: actions must be a torch tensor')
-        n, na = self.num_envs, self.action_dim
-        if actions.dim() == 2:
-            if steps is None:
-                raise ValueError('rollout: (N, A) actions need steps=T')
-            T, stride = int(steps), 0
-            want = (n, na)
-        else:
-            T = int(actions.shape[0]) if actions.dim() == 3 else 0
-            if steps is not None and int(steps) != T:
-                raise ValueError(f'rollout: steps={steps} but actions hold {T} steps')
-            stride = n * na
-            want = (T, n, na)
-        if T <= 0 or tuple(actions.shape) != want:
-            raise ValueError(f'rollout: actions must have shape (T, {n}, {na}) or ({n}, {na}) with steps=T >= 1, '
-                             f'got {tuple(actions.shape)}')
-        if stop_at_done and self._auto_reset:
-            raise ValueError('rollout: stop_at_done needs auto-reset off')
-        a = actions
-        if a.dtype != self.dtype or a.device != self.device or not a.is_contiguous():
-            a = a.to(device=self.device, dtype=self.dtype).contiguous()
-        out = dict(out or {})
-        unknown = set(out) - {'obs', 'reward', 'done', 'info'}
-        if unknown:
-            raise ValueError(f'rollout: unknown out buffers {sorted(unknown)}')
-        shapes = {'reward': ((T, n), self.dtype), 'done': ((T, n), torch.uint8)}
-        if obs == 'all':
-            shapes['obs'] = ((T, n, self.obs_dim), self.dtype)
-        if info:
-            shapes['info'] = ((T, n, self.info_dim), self.dtype)
-        for k in out:
-            if k not in shapes:
-                raise ValueError(f"rollout: out['{k}'] given but not asked for (obs={obs!r}, info={info})")
-        buf = {}
-        for k, (shape, dtype) in shapes.items():
-            if k in out:
-                buf[k] = self._check_seq(out[k], shape, dtype, f"out['{k}']")
-            else:
-                buf[k] = torch.empty(shape, dtype=dtype, device=self.device)
+        a, T, stride, buf = _rollout_buffers(self, actions, steps, obs, info, stop_at_done and self._auto_reset, out,
+                                             zero=False)
         obs_seq, obs_last = buf.get('obs'), (self.obs if obs is not None else None)
         if getattr(self, '_storage_grow', 0):
             self._apply_storage_growth()
@@ -618,7 +629,10 @@ class MixedVectorEnv:
     launch per segment, in order, on the first segment's stream.
     Device-drawn reset rows are keyed by the global env index (``env_offset``
     + row), as in :class:`VectorEnv`, so the batch reproduces each segment
-    stepped alone bit for bit."""
+    stepped alone bit for bit.  ``rollout`` runs T such steps from an action
+    plan in one call (``bioim_rollout_group``); per-env resets, the active
+    mask and the state calls (``state_rows``, ``load_state``, ``clone_envs``)
+    take global env ids and dispatch to the segments."""
 
     def __init__(self, segments, config=None, device: int = 0, precision: int = 64, seed: int = 0,
                  auto_reset: bool = False, env_offset: int = 0):
@@ -652,6 +666,7 @@ class MixedVectorEnv:
             off += e.num_envs
         self._hs = (C.c_void_p * len(self.envs))(*[e._h.value for e in self.envs])
         self._L = self.envs[0]._L
+        self._auto_reset = bool(auto_reset)
 
     @property
     def build_id(self) -> str:
@@ -663,10 +678,178 @@ class MixedVectorEnv:
         (bioim_group_fused) rather than one launch per segment"""
         return _lib.check(self._L.bioim_group_fused(self.envs[0]._h)) == 1
 
-    def reset(self):
-        for e in self.envs:
-            e.reset()
+    def _global_ids(self, ids, what, distinct):
+        """global env ids (list, range, numpy array or tensor) as a host int64
+        array: integers in [0, num_envs), with ``distinct`` not repeating"""
+        import torch
+        if isinstance(ids, torch.Tensor):
+            if ids.dtype in (torch.bool, torch.float16, torch.bfloat16, torch.float32, torch.float64):
+                raise ValueError(f'{what} ids must be integers, got {ids.dtype}')
+            ids = ids.detach().cpu().numpy()
+        host = np.asarray(ids).reshape(-1)
+        if host.size and host.dtype.kind not in 'iu':
+            raise ValueError(f'{what} ids must be integers, got {host.dtype}')
+        host = host.astype(np.int64)
+        if host.size and (host.min() < 0 or host.max() >= self.num_envs):
+            raise ValueError(f'{what} ids must lie in [0, {self.num_envs})')
+        if distinct and np.unique(host).size != host.size:
+            raise ValueError(f'{what} ids must be distinct')
+        return host
+
+    def _split(self, host):
+        """(segment env, positions in the list, segment-local ids) for every
+        segment that owns some of the global ids ``host``, in segment order;
+        the list's order is kept within a segment"""
+        seg = self._segment_of(host)
+        for i, e in enumerate(self.envs):
+            pos = np.nonzero(seg == i)[0]
+            if pos.size:
+                yield e, pos, host[pos] - self.offsets[i]
+
+    def _segment_of(self, host):
+        """the index of the segment that owns each global id"""
+        return np.searchsorted(np.asarray(self.offsets[1:], dtype=np.int64), host, side='right')
+
+    def _upload_index(self, host):
+        """host positions as an int64 device tensor, copied from pinned memory
+        on the current stream without waiting for the device"""
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(host, dtype=np.int64)).pin_memory().to(self.device, non_blocking=True)
+
+    def reset(self, env_ids=None, ref_index=None):
+        """Reset the listed envs (global ids; default all).  ref_index: one
+        reference row per listed env (default: drawn on the device).  Each
+        segment resets its own envs, as ``VectorEnv.reset``."""
+        if env_ids is None and ref_index is None:
+            for e in self.envs:
+                e.reset()
+            return self.obs
+        host = np.arange(self.num_envs, dtype=np.int64) if env_ids is None else self._global_ids(env_ids, 'env', distinct=True)
+        rows = None
+        if ref_index is not None:
+            rows = np.asarray(ref_index.detach().cpu().numpy() if hasattr(ref_index, 'detach') else ref_index).reshape(-1)
+            if rows.size != host.size:
+                raise ValueError(f'reset: {rows.size} ref_index rows for {host.size} envs')
+        for e, pos, local in self._split(host):
+            e.reset(local, None if rows is None else rows[pos])
         return self.obs
+
+    def set_auto_reset(self, on: bool):
+        for e in self.envs:
+            e.set_auto_reset(on)
+        self._auto_reset = bool(on)
+
+    def set_active_mask(self, mask):
+        """Per-env step mask over the whole batch: a (N,) uint8/bool device
+        tensor (``check_env_mask``), handed to the segments' handles in
+        slices; ``None`` steps all.  The tensor must stay alive while set."""
+        check_env_mask(mask, self.num_envs, self.device)
+        self._active = mask
+        for e, off in zip(self.envs, self.offsets):
+            e.set_active_mask(None if mask is None else mask[off:off + e.num_envs])
+
+    @property
+    def state_dim(self) -> int:
+        """width of the padded state rows: the largest of the segments'"""
+        return max(e.state_dim for e in self.envs)
+
+    @property
+    def state_mask(self):
+        """(N, state_dim) bool: each row's valid columns (its segment's own state_dim)"""
+        import torch
+        m = torch.zeros((self.num_envs, self.state_dim), dtype=torch.bool, device=self.device)
+        for e, off in zip(self.envs, self.offsets):
+            m[off:off + e.num_envs, :e.state_dim] = True
+        return m
+
+    _check_rows = VectorEnv._check_rows      # uses only state_dim and device
+
+    def state_rows(self, out=None, env_ids=None):
+        """The flat state rows of the listed envs (global ids; default all) as
+        (n, state_dim) float64, in the list's order, each row zero-padded past
+        its segment's own state_dim (``state_mask``).  One
+        ``bioim_copy_state_rows`` launch per segment on the shared stream; no
+        synchronization."""
+        import torch
+        host = np.arange(self.num_envs, dtype=np.int64) if env_ids is None else self._global_ids(env_ids, 'env', distinct=False)
+        n, sd = host.size, self.state_dim
+        if out is None:
+            out = torch.zeros((n, sd), dtype=torch.float64, device=self.device)
+        else:
+            self._check_rows(out, n, 'state_rows: out')
+        for e, pos, local in self._split(host):
+            rows = e.state_rows(env_ids=local)
+            at = self._upload_index(pos)
+            out[at, :e.state_dim] = rows
+            if e.state_dim < sd:
+                out[at, e.state_dim:] = 0
+        return out
+
+    def load_state(self, rows, env_ids=None):
+        """Write padded state rows (``state_rows``' layout) into the listed
+        envs (global, distinct ids; default all in order): one
+        ``bioim_load_state`` launch per segment on the shared stream; no
+        synchronization.  Columns past a segment's state_dim are ignored."""
+        host = np.arange(self.num_envs, dtype=np.int64) if env_ids is None else self._global_ids(env_ids, 'env', distinct=True)
+        self._check_rows(rows, host.size, 'load_state: rows')
+        for e, pos, local in self._split(host):
+            sub = rows.index_select(0, self._upload_index(pos))[:, :e.state_dim].contiguous()
+            e.load_state(sub, local)
+
+    def clone_envs(self, src, dst):
+        """``VectorEnv.clone_envs`` with global ids: every dst env becomes an
+        exact copy of its src env (an int: one source for all), one
+        ``bioim_clone_envs`` launch per segment.  A pair must lie in one
+        segment (the records of two env IDs differ): else ``ValueError``."""
+        dst_h = self._global_ids(dst, 'dst', distinct=True)
+        if isinstance(src, (int, np.integer)):
+            src = np.full(dst_h.size, int(src), dtype=np.int64)
+        src_h = self._global_ids(src, 'src', distinct=False)
+        if src_h.size != dst_h.size:
+            raise ValueError(f'clone_envs: {src_h.size} src ids for {dst_h.size} dst ids')
+        if np.intersect1d(src_h, dst_h).size:
+            raise ValueError('clone_envs: an env cannot be both a src and a dst')
+        if np.any(self._segment_of(src_h) != self._segment_of(dst_h)):
+            raise ValueError('clone_envs: a src and its dst must lie in one segment')
+        for e, pos, local in self._split(dst_h):
+            e.clone_envs(src_h[pos] - e.env_offset + self.envs[0].env_offset, local)
+
+    def rollout(self, actions, steps=None, *, obs='last', info=False, stop_at_done=False, out=None):
+        """``VectorEnv.rollout`` for the mixed batch (``bioim_rollout_group``):
+        T consecutive env steps from an action sequence, enqueued by one call,
+        bit for bit what T ``step()`` calls give.  N is the batch total and A,
+        O, I the padded widths: ``actions`` (T, N, A), or (N, A) with
+        ``steps=T``; ``obs`` 'last' (written to ``self.obs``), 'all'
+        ((T, N, O); ``self.obs`` gets the last rows too) or None; ``info``:
+        also the (T, N, I) rows; ``stop_at_done`` (auto-reset off only) per
+        env, each segment's active mask honoured and left alone; ``out``: a
+        dict of caller buffers ('reward' (T, N), 'done' (T, N) uint8, 'obs',
+        'info').  Buffers allocated here are zero-filled, so the padding
+        columns are zero; those of caller buffers are left alone.  With two
+        segments of a fused pair in the default step configuration the call
+        is ONE kernel launch, otherwise T group steps enqueued from C — see
+        ``last_rollout_fused``.
+
+        Returns (obs, reward (T, N), done (T, N) uint8, info or None)."""
+        a, T, stride, buf = _rollout_buffers(self, actions, steps, obs, info,
+                                             stop_at_done and any(e._auto_reset for e in self.envs), out, zero=True)
+        obs_seq, obs_last = buf.get('obs'), (self.obs if obs is not None else None)
+        for e in self.envs:
+            if getattr(e, '_storage_grow', 0):
+                e._apply_storage_growth()
+        p = VectorEnv._ptr
+        self.envs[0]._bind_stream()      # as step(): the call is ordered on segment 0's stream
+        _lib.check(self._L.bioim_rollout_group(self._hs, len(self.envs), p(a), T, stride, p(obs_seq), p(obs_last),
+                                               p(buf['reward']), p(buf['done']), p(buf.get('info')),
+                                               1 if stop_at_done else 0))
+        return (self.obs if obs == 'last' else obs_seq), buf['reward'], buf['done'], buf.get('info')
+
+    @property
+    def last_rollout_fused(self) -> bool:
+        """True if the last ``rollout()`` ran as ONE launch of the
+        two-topology rollout kernel, False if it looped over the group steps
+        (bioim_rollout_group_fused)."""
+        return bool(_lib.check(self._L.bioim_rollout_group_fused(self.envs[0]._h)))
 
     def step(self, actions):
         """actions: (N, max A) tensor; columns beyond a row's own action dim are ignored."""

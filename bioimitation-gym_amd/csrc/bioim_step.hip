@@ -3846,8 +3846,128 @@ meet:
     }
 }
 
+/* Fused multi-step rollout of a two-segment mixed batch (bioim_rollout_group):
+ * rollout_kernel crossed with env_kernel2.  Workgroups [0, a0.blocks) run
+ * segment 0's rollout loop with topology T0, the rest segment 1's with T1, on
+ * the block index counted from the segment's first workgroup.  Each segment's
+ * base pointers (a0 / a1 and r0 / r1) are already offset by its first row of
+ * the padded full-batch buffers, so env indices stay segment-local; only the
+ * per-step pitch of the sequence buffers is the whole batch's: `rows` rows,
+ * not the segment's a.N.  The loop is rollout_kernel's, with every register
+ * measure it takes; it is a separate body, so that kernel's
+ * code stays as it is.  Every thread of a workgroup takes the same branch:
+ * the barriers stay uniform. */
+template <class T, typename Real>
+DEV LaunchArgs<T, Real> rollout2_step_args(const LaunchArgs<T, Real> &a0, const RolloutSeq<Real> &r, int k, size_t rows) {
+    LaunchArgs<T, Real> a = a0;
+    a.actions = a0.actions + (size_t)k * (size_t)r.act_step;
+    a.obs = r.obs_seq ? r.obs_seq + (size_t)k * rows * a0.obs_stride
+                      : (k == r.steps - 1 || r.stop_at_done ? r.obs_last : nullptr);
+    a.reward = r.reward_seq ? r.reward_seq + (size_t)k * rows : nullptr;
+    a.done_out = r.done_seq + (size_t)k * rows;
+    a.info = r.info_seq ? r.info_seq + (size_t)k * rows * a0.info_stride : nullptr;
+    if (r.stop_at_done) a.active = r.live;
+    return a;
+}
+
+/* rollout_thread with the segment's first workgroup `blk0` (a scalar) taken
+ * off the block index */
+template <class T> DEV void rollout2_thread(int wave, int blk0, int &lane, int &env) {
+    static_assert(BIOIM_EPB * T::G % 64 == 0, "whole waves");
+    int in_wave;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(in_wave));
+    const int tid = wave * 64 + in_wave;
+    lane = tid % T::G;
+    env = ((int)blockIdx.x - blk0) * BIOIM_EPB + tid / T::G;
+}
+
+template <class T, typename Real>
+DEV void rollout2_segment(const LaunchArgs<T, Real> &a0, const RolloutSeq<Real> &r, const int wave, const int blk0,
+                          const int rows_total) {
+    constexpr int G = T::G;
+    static_assert(G <= 64, "an env's lane group lies in one wave (the mask below is read, then cleared, in program order)");
+    const size_t rows = (size_t)rows_total;
+    if (r.stop_at_done) {
+        int lane, env;
+        rollout2_thread<T>(wave, blk0, lane, env);
+        if (env < a0.N && lane == 0) r.live[env] = !r.active || r.active[env] != 0 ? 1 : 0;
+    }
+    /* the never-taken second loop entry and the opaque scalar operands of
+     * rollout_kernel, for the reasons given there */
+    int k = 0, blk = (int)blockIdx.x - blk0;
+    LaunchArgs<T, Real> a = a0;
+    if (r.steps <= 0) goto meet;
+step:
+    {
+        a = rollout2_step_args<T, Real>(a0, r, k, rows);
+        blk = (int)blockIdx.x - blk0;
+        asm volatile("" : "+s"(blk));
+        asm volatile("" : "+s"(a.N));
+        asm volatile("" : "+s"(a.Mg));
+        asm volatile("" : "+s"(a.Sg));
+        asm volatile("" : "+s"(a.act_stride), "+s"(a.obs_stride), "+s"(a.info_stride));
+        asm volatile("" : "+s"(a.st.q), "+s"(a.st.u), "+s"(a.st.act), "+s"(a.st.lce), "+s"(a.st.hist), "+s"(a.st.last));
+        asm volatile("" : "+s"(a.st.vnw), "+s"(a.st.cache), "+s"(a.st.cache_ok));
+        env_block<T, Real, false, false, false>(a, blk);
+    }
+meet:
+    {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __syncthreads();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        if (r.stop_at_done) {
+            int lane, env;
+            rollout2_thread<T>(wave, blk0, lane, env);
+            if (env < a0.N && (!r.active || r.active[env] != 0)) {
+                if (r.live[env]) {   /* stepped just now */
+                    if (a.done_out[env] && lane == 0) r.live[env] = 0;
+                } else {
+                    if (lane == 0) {
+                        if (a.reward) a.reward[env] = Real(0);
+                        a.done_out[env] = 1;
+                    }
+                    if (a.info && lane < a0.Mg->info_dim) a.info[(size_t)env * a0.info_stride + lane] = Real(0);
+                    if (r.obs_seq) {
+                        /* the previous step's row: one whole batch of rows back */
+                        Real *row = a.obs + (size_t)env * a0.obs_stride;
+                        const Real *prev = row - rows * a0.obs_stride;
+                        for (int j = lane; j < a0.Mg->obs_dim; j += G) row[j] = prev[j];
+                    }
+                }
+            }
+        }
+        if (++k < r.steps) goto step;
+    }
+    if (r.obs_seq && r.obs_last) {
+        int lane, env;
+        rollout2_thread<T>(wave, blk0, lane, env);
+        if (env < a0.N && (!a0.active || a0.active[env] != 0)) {
+            const Real *last = r.obs_seq + ((size_t)(r.steps - 1) * rows + env) * a0.obs_stride;
+            Real *row = r.obs_last + (size_t)env * a0.obs_stride;
+            for (int j = lane; j < a0.Mg->obs_dim; j += G) row[j] = last[j];
+        }
+    }
+}
+
+template <class T0, class T1, typename Real>
+__global__ __launch_bounds__(BIOIM_EPB * T0::G) __attribute__((amdgpu_waves_per_eu(1, 1))) void rollout_kernel2(
+    LaunchArgs<T0, Real> a0, RolloutSeq<Real> r0, LaunchArgs<T1, Real> a1, RolloutSeq<Real> r1, int rows_total) {
+    static_assert(T0::G == T1::G, "a fused launch needs one workgroup shape");
+    const int wave = rollout_wave();
+    if ((int)blockIdx.x < a0.blocks) rollout2_segment<T0, Real>(a0, r0, wave, 0, rows_total);
+    else rollout2_segment<T1, Real>(a1, r1, wave, a0.blocks, rows_total);
+}
+
 #define BIOIM_FUSED_PAIRS(X)                                                         \
     X(Topo_MuscleLockedKneeImitation3D_v0, Topo_MuscleWalkingImitation3D_v0)          \
+    X(Topo_MuscleWalkingImitation3D_v0, Topo_MuscleLockedKneeImitation3D_v0)
+
+/* The pairs rollout_kernel2 is instantiated for.  A group of BIOIM_FUSED_PAIRS
+ * in the other order runs the same instantiation with the two argument sets
+ * swapped (which segment takes the low block indices changes no result): the
+ * <LockedKnee3D, Walking3D> instantiation did not clear the hazard gate
+ * (DESIGN.md 5.13). */
+#define BIOIM_ROLLOUT_PAIRS(X)                                                       \
     X(Topo_MuscleWalkingImitation3D_v0, Topo_MuscleLockedKneeImitation3D_v0)
 
 /* =================================================================== host
@@ -4299,6 +4419,7 @@ struct bioim_handle {
     int cache_live;       /* a default step kernel ran since the realize-cache flags were last cleared */
     uint8_t *rollout_live; /* bioim_rollout stop_at_done: scratch mask [n], allocated on first use */
     int last_rollout_fused; /* the last bioim_rollout ran as one launch of the rollout kernel */
+    int last_rollout_group_fused; /* the last bioim_rollout_group with this handle first ran as one launch */
     Ops ops;
     bioim_modelpack_t pack;
 };
@@ -4463,6 +4584,52 @@ void rollout_launch_impl(bioim_handle_t *h, const RolloutCall &c) {
     hipLaunchKernelGGL((rollout_kernel<T, Real>), dim3(a.blocks), dim3(BIOIM_EPB * T::G), lds, h->stream, a, r);
 }
 
+/* one segment's arguments of a rollout_kernel2 launch: handle h owns the rows
+ * from `off` on of the padded full-batch buffers of c */
+template <class T, typename Real>
+void rollout2_segment_args(bioim_handle_t *h, const RolloutCall &c, size_t off, LaunchArgs<T, Real> &a, RolloutSeq<Real> &r) {
+    const Real *actions = reinterpret_cast<const Real *>(c.actions) + off * h->act_stride;
+    Real *obs_seq = reinterpret_cast<Real *>(c.obs_seq), *obs_last = reinterpret_cast<Real *>(c.obs_last);
+    Real *reward_seq = reinterpret_cast<Real *>(c.reward_seq), *info_seq = reinterpret_cast<Real *>(c.info_seq);
+    a = make_args<T, Real>(h, 0, actions, nullptr, nullptr, c.done_seq + off, nullptr, nullptr, nullptr, 0, nullptr);
+    r.steps = c.steps; r.stop_at_done = c.stop_at_done; r.act_step = c.act_step;
+    r.obs_seq = obs_seq ? obs_seq + off * h->obs_stride : nullptr;
+    r.obs_last = obs_last ? obs_last + off * h->obs_stride : nullptr;
+    r.reward_seq = reward_seq ? reward_seq + off : nullptr;
+    r.done_seq = c.done_seq + off;
+    r.info_seq = info_seq ? info_seq + off * h->info_stride : nullptr;
+    r.live = h->rollout_live; r.active = h->active;
+}
+
+/* one launch of rollout_kernel2 for a two-segment group rollout: h0 (topology
+ * T0, rows from off0 on) takes the low block indices, h1 (T1, rows from off1
+ * on) the rest; `rows` is the whole batch's row count, the sequence buffers'
+ * per-step pitch; on `stream` (the group's first handle's) */
+template <class T0, class T1, typename Real>
+int rollout2_launch_impl(bioim_handle_t *h0, size_t off0, bioim_handle_t *h1, size_t off1, const RolloutCall &c, int rows,
+                         hipStream_t stream) {
+    LaunchArgs<T0, Real> a0;
+    LaunchArgs<T1, Real> a1;
+    RolloutSeq<Real> r0, r1;
+    rollout2_segment_args<T0, Real>(h0, c, off0, a0, r0);
+    rollout2_segment_args<T1, Real>(h1, c, off1, a1, r1);
+    constexpr size_t l0 = lds_bytes<T0, Real, false>(), l1 = lds_bytes<T1, Real, false>();
+    constexpr size_t lds = l0 > l1 ? l0 : l1;
+    static_assert(lds <= 163840, "LDS image + env regions exceed 160 KiB");
+    static bool attr[64] = {};   /* the dynamic-LDS attribute is per device */
+    const int dev = h0->device;
+    if (dev < 0 || dev >= 64 || !attr[dev]) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&rollout_kernel2<T0, T1, Real>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (dev >= 0 && dev < 64) attr[dev] = true;
+    }
+    if (a0.blocks + a1.blocks <= 0) return 0;
+    h0->cache_live = 1; h1->cache_live = 1;   /* default step code: it forms the realize cache */
+    hipLaunchKernelGGL((rollout_kernel2<T0, T1, Real>), dim3(a0.blocks + a1.blocks), dim3(BIOIM_EPB * T0::G), lds, stream,
+                       a0, r0, a1, r1, rows);
+    return 0;
+}
+
 template <class T, typename Real>
 void id_launch_impl(bioim_handle_t *h, int op, int n, const void *q, const void *u, const void *v, void *out) {
     constexpr int EPB = BIOIM_EPB;
@@ -4551,6 +4718,30 @@ int bioim_fused_launch(bioim_handle_t *h0, bioim_handle_t *h1, const void *actio
         return rc ? rc : 1;                                                                          \
     }
     BIOIM_FUSED_PAIRS(BIOIM_TRY_PAIR)
+#undef BIOIM_TRY_PAIR
+    return 0;
+}
+#endif
+/* the fused two-segment rollout (the fused unit, or all in this TU): h0 owns
+ * rows [0, n0) of c's padded full-batch buffers, h1 the rows after them.
+ * 1 if the pair has a rollout_kernel2 instantiation (BIOIM_ROLLOUT_PAIRS, in
+ * either order) and was launched on h0's stream, 0 if not */
+int bioim_rollout2_launch(bioim_handle_t *h0, bioim_handle_t *h1, const RolloutCall &c);
+#if defined(BIOIM_FUSED_ONLY) || (!defined(BIOIM_TOPO_ONLY) && !defined(BIOIM_ABI_ONLY))
+int bioim_rollout2_launch(bioim_handle_t *h0, bioim_handle_t *h1, const RolloutCall &c) {
+    if (h0->precision != 64) return 0;   /* as bioim_fused_launch */
+    const size_t n0 = (size_t)h0->n;
+    const int rows = h0->n + h1->n;
+#define BIOIM_TRY_PAIR(S0, S1)                                                                                  \
+    if (!strcmp(h0->ops.topo, #S0) && !strcmp(h1->ops.topo, #S1)) {                                              \
+        const int rc = rollout2_launch_impl<S0, S1, double>(h0, 0, h1, n0, c, rows, h0->stream);                 \
+        return rc ? rc : 1;                                                                                      \
+    }                                                                                                            \
+    if (!strcmp(h0->ops.topo, #S1) && !strcmp(h1->ops.topo, #S0)) {   /* the argument sets swapped */            \
+        const int rc = rollout2_launch_impl<S0, S1, double>(h1, n0, h0, 0, c, rows, h0->stream);                 \
+        return rc ? rc : 1;                                                                                      \
+    }
+    BIOIM_ROLLOUT_PAIRS(BIOIM_TRY_PAIR)
 #undef BIOIM_TRY_PAIR
     return 0;
 }
@@ -4799,7 +4990,7 @@ int bioim_create(const bioim_modelpack_t *pack, int n_envs, int device, int prec
     h->env_offset = 0;
     h->pert_n = 0; h->pert_ob = -1;
     h->reset_tab = nullptr; h->reset_tab_on = 1; h->cache_live = 0;
-    h->rollout_live = nullptr; h->last_rollout_fused = 0;
+    h->rollout_live = nullptr; h->last_rollout_fused = 0; h->last_rollout_group_fused = 0;
     h->planar = pack_is_planar(*pack) ? 1 : 0;
     h->act_stride = pack->nact; h->obs_stride = pack->obs_dim; h->info_stride = pack->info_dim;
     h->ops = ops;
@@ -5067,31 +5258,23 @@ int bioim_group_fused(const bioim_handle_t *h) {
     return h->last_group_fused ? 1 : 0;
 }
 
-int bioim_step_group(bioim_handle_t **hs, int nh, const void *actions, void *obs, void *reward, uint8_t *done,
-                     void *info) {
-    if (!hs || nh <= 0 || !actions || !done) return fail(BIOIM_E_ARG, "bioim_step_group: bad arguments");
-    for (int i = 0; i < nh; ++i) {
-        if (!hs[i]) return fail(BIOIM_E_ARG, "bioim_step_group: null handle");
-        if (hs[i]->device != hs[0]->device || hs[i]->precision != hs[0]->precision ||
-            hs[i]->act_stride != hs[0]->act_stride || hs[i]->obs_stride != hs[0]->obs_stride ||
-            hs[i]->info_stride != hs[0]->info_stride)
-            return fail(BIOIM_E_ARG, "bioim_step_group: handles differ in device, precision or I/O strides");
-    }
-    HIPCHK(hipSetDevice(hs[0]->device));
-    for (int i = 0; i < nh; ++i)
-        if (const int rc = ensure_reset_table(hs[i])) return rc;
+/* one step of a group, enqueued (bioim_step_group after its checks; each step
+ * of bioim_rollout_group's host loop): the fused two-topology launch where
+ * eligible (*fused = 1), else one launch per segment, forked and joined */
+static int group_step_enqueue(bioim_handle_t **hs, int nh, const void *actions, void *obs, void *reward, uint8_t *done,
+                              void *info, int *fused) {
     const size_t R = hs[0]->precision == 64 ? 8 : 4;
     hipStream_t stream = hs[0]->stream;
     /* two segments whose topology pair has a fused kernel (BIOIM_FUSED_PAIRS)
      * and that run the default step kernels (no push table, semi-implicit):
      * one launch, workgroups [0, B0) segment 0, the rest segment 1 */
-    hs[0]->last_group_fused = 0;
+    *fused = 0;
     if (nh == 2 && g_group_fusion && hs[0]->pert_n == 0 && hs[1]->pert_n == 0 && !hs[0]->rk && !hs[1]->rk) {
         const int rc = bioim_fused_launch(hs[0], hs[1], actions, obs, reward, done, info);
         if (rc < 0) return rc;
         if (rc == 1) {
             HIPCHK(hipGetLastError());
-            hs[0]->last_group_fused = 1;
+            *fused = 1;
             return 0;
         }
     }
@@ -5121,6 +5304,25 @@ int bioim_step_group(bioim_handle_t **hs, int nh, const void *actions, void *obs
     }
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+int bioim_step_group(bioim_handle_t **hs, int nh, const void *actions, void *obs, void *reward, uint8_t *done,
+                     void *info) {
+    if (!hs || nh <= 0 || !actions || !done) return fail(BIOIM_E_ARG, "bioim_step_group: bad arguments");
+    for (int i = 0; i < nh; ++i) {
+        if (!hs[i]) return fail(BIOIM_E_ARG, "bioim_step_group: null handle");
+        if (hs[i]->device != hs[0]->device || hs[i]->precision != hs[0]->precision ||
+            hs[i]->act_stride != hs[0]->act_stride || hs[i]->obs_stride != hs[0]->obs_stride ||
+            hs[i]->info_stride != hs[0]->info_stride)
+            return fail(BIOIM_E_ARG, "bioim_step_group: handles differ in device, precision or I/O strides");
+    }
+    HIPCHK(hipSetDevice(hs[0]->device));
+    for (int i = 0; i < nh; ++i)
+        if (const int rc = ensure_reset_table(hs[i])) return rc;
+    int fused = 0;
+    const int rc = group_step_enqueue(hs, nh, actions, obs, reward, done, info, &fused);
+    hs[0]->last_group_fused = fused;
+    return rc;
 }
 
 int bioim_set_perturbation(bioim_handle_t *h, int os_body, int npts, const double *x, const double *y) {
@@ -5617,6 +5819,133 @@ int bioim_rollout(bioim_handle_t *h, const void *actions, int steps, int64_t act
 int bioim_rollout_fused(const bioim_handle_t *h) {
     if (!h) return fail(BIOIM_E_ARG, "bioim_rollout_fused: null handle");
     return h->last_rollout_fused ? 1 : 0;
+}
+
+/* bioim_rollout_group's host-loop path: per step what bioim_step_group
+ * enqueues, then (stop_at_done) the freeze kernel per segment on hs[0]'s
+ * stream, after the join, on that step's slices at the full-batch pitch */
+extern "C++" {
+template <typename Real> static int rollout_group_host_loop(bioim_handle_t **hs, int nh, const RolloutCall &c, size_t rows) {
+    hipStream_t stream = hs[0]->stream;
+    const size_t os = (size_t)hs[0]->obs_stride, is = (size_t)hs[0]->info_stride;
+    const Real *actions = reinterpret_cast<const Real *>(c.actions);
+    Real *obs_seq = reinterpret_cast<Real *>(c.obs_seq), *obs_last = reinterpret_cast<Real *>(c.obs_last);
+    Real *reward_seq = reinterpret_cast<Real *>(c.reward_seq), *info_seq = reinterpret_cast<Real *>(c.info_seq);
+    std::vector<const uint8_t *> user_active(nh);
+    for (int i = 0; i < nh; ++i) user_active[i] = hs[i]->active;
+    if (c.stop_at_done)
+        for (int i = 0; i < nh; ++i) {
+            bioim_handle_t *h = hs[i];
+            if (h->n > 0)
+                hipLaunchKernelGGL(rollout_live_init, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, stream,
+                                   h->rollout_live, user_active[i], h->n);
+            h->active = h->rollout_live;
+        }
+    int rc = 0;
+    for (int k = 0; k < c.steps && !rc; ++k) {
+        Real *obs = obs_seq ? obs_seq + (size_t)k * rows * os : (k == c.steps - 1 || c.stop_at_done ? obs_last : nullptr);
+        Real *reward = reward_seq ? reward_seq + (size_t)k * rows : nullptr;
+        uint8_t *done = c.done_seq + (size_t)k * rows;
+        Real *info = info_seq ? info_seq + (size_t)k * rows * is : nullptr;
+        int fused = 0;
+        rc = group_step_enqueue(hs, nh, actions + (size_t)k * (size_t)c.act_step, obs, reward, done, info, &fused);
+        if (rc || !c.stop_at_done) continue;
+        size_t off = 0;
+        for (int i = 0; i < nh; ++i) {
+            bioim_handle_t *h = hs[i];
+            Real *so = obs_seq ? obs + off * os : nullptr;
+            if (h->n > 0)
+                hipLaunchKernelGGL((rollout_freeze_kernel<Real>), dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, stream,
+                                   h->rollout_live, user_active[i], h->n, done + off, reward ? reward + off : nullptr,
+                                   info ? info + off * is : nullptr, h->info_dim, h->info_stride, so,
+                                   so && k > 0 ? so - rows * os : nullptr, h->obs_dim, h->obs_stride);
+            off += (size_t)h->n;
+        }
+    }
+    for (int i = 0; i < nh; ++i) hs[i]->active = user_active[i];
+    if (rc) return rc;
+    if (obs_seq && obs_last) {
+        size_t off = 0;
+        for (int i = 0; i < nh; ++i) {
+            bioim_handle_t *h = hs[i];
+            const size_t cnt = (size_t)h->n * h->obs_dim;
+            if (cnt > 0)
+                hipLaunchKernelGGL((rollout_obs_last_kernel<Real>), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream,
+                                   user_active[i], h->n, obs_seq + ((size_t)(c.steps - 1) * rows + off) * os,
+                                   obs_last + off * os, h->obs_dim, h->obs_stride);
+            off += (size_t)h->n;
+        }
+    }
+    return 0;
+}
+}  // extern "C++"
+
+int bioim_rollout_group(bioim_handle_t **hs, int nh, const void *actions, int steps, int64_t action_step_stride,
+                        void *obs_seq, void *obs_last, void *reward_seq, uint8_t *done_seq, void *info_seq,
+                        int stop_at_done) {
+    if (!hs || nh <= 0) return fail(BIOIM_E_ARG, "bioim_rollout_group: null handle list or nh <= 0");
+    for (int i = 0; i < nh; ++i)
+        if (!hs[i]) return fail(BIOIM_E_ARG, "bioim_rollout_group: null handle");
+    if (!actions || !done_seq) return fail(BIOIM_E_ARG, "bioim_rollout_group: null actions or done_seq");
+    if (steps <= 0) return fail(BIOIM_E_ARG, "bioim_rollout_group: steps must be positive");
+    if (action_step_stride < 0) return fail(BIOIM_E_ARG, "bioim_rollout_group: negative action_step_stride");
+    size_t rows = 0;
+    for (int i = 0; i < nh; ++i) {
+        const bioim_handle_t *h = hs[i];
+        if (h->device != hs[0]->device || h->precision != hs[0]->precision || h->act_stride != hs[0]->act_stride ||
+            h->obs_stride != hs[0]->obs_stride || h->info_stride != hs[0]->info_stride)
+            return fail(BIOIM_E_ARG, "bioim_rollout_group: handles differ in device, precision or I/O strides");
+        if (h->rk && h->rk_budget > 0)
+            return fail(BIOIM_E_ARG, "bioim_rollout_group: a budgeted RK handle suspends envs mid-step, a rollout has no rows "
+                                     "for that (bioim_set_rk_budget(h, 0, NULL) first)");
+        if (stop_at_done && h->auto_reset)
+            return fail(BIOIM_E_ARG, "bioim_rollout_group: stop_at_done needs auto-reset off (a reset env goes on)");
+        rows += (size_t)h->n;
+    }
+    if (nh == 1) {   /* one segment: bioim_rollout */
+        const int rc = bioim_rollout(hs[0], actions, steps, action_step_stride, obs_seq, obs_last, reward_seq, done_seq,
+                                     info_seq, stop_at_done);
+        if (rc == 0) hs[0]->last_rollout_group_fused = hs[0]->last_rollout_fused;
+        return rc;
+    }
+    HIPCHK(hipSetDevice(hs[0]->device));
+    for (int i = 0; i < nh; ++i) {
+        bioim_handle_t *h = hs[i];
+        if (h->rk) {   /* only an RK handle can hold suspended envs; the count waits for its stream */
+            const int np = bioim_pending_count(h);
+            if (np < 0) return np;
+            if (np > 0) return fail(BIOIM_E_ARG, "bioim_rollout_group: envs are suspended mid-step (bioim_set_rk_budget)");
+        }
+        if (const int rc = ensure_reset_table(h)) return rc;
+        if (stop_at_done && !h->rollout_live && h->n > 0)
+            HIPCHK(hipMalloc(reinterpret_cast<void **>(&h->rollout_live), (size_t)h->n));
+    }
+    const RolloutCall c{actions, steps, action_step_stride, obs_seq, obs_last, reward_seq, done_seq, info_seq,
+                        stop_at_done ? 1 : 0};
+    hs[0]->last_rollout_group_fused = 0;
+    /* ONE launch of rollout_kernel2 exactly where bioim_step_group would fuse
+     * (two segments, fusion on, fp64 and a fused pair — bioim_rollout2_launch
+     * answers those two —, no push table, not RK) and neither handle has a
+     * force report or state storage */
+    if (nh == 2 && g_group_fusion && rollout_fusable(hs[0]) && rollout_fusable(hs[1])) {
+        const int rc = bioim_rollout2_launch(hs[0], hs[1], c);
+        if (rc < 0) return rc;
+        if (rc == 1) {
+            HIPCHK(hipGetLastError());
+            hs[0]->last_rollout_group_fused = 1;
+            return 0;
+        }
+    }
+    const int rc = hs[0]->precision == 64 ? rollout_group_host_loop<double>(hs, nh, c, rows)
+                                          : rollout_group_host_loop<float>(hs, nh, c, rows);
+    if (rc) return rc;
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int bioim_rollout_group_fused(const bioim_handle_t *h) {
+    if (!h) return fail(BIOIM_E_ARG, "bioim_rollout_group_fused: null handle");
+    return h->last_rollout_group_fused ? 1 : 0;
 }
 
 int bioim_sync(bioim_handle_t *h) {

@@ -324,6 +324,54 @@ int bioim_rollout(bioim_handle_t *h, const void *actions, int steps, int64_t act
 /* 1 if the last bioim_rollout on h ran as one launch of the rollout kernel, 0
  * if it looped over the step kernels (or none ran yet); -1 for a null handle. */
 int bioim_rollout_fused(const bioim_handle_t *h);
+/* bioim_rollout_group: `steps` consecutive env steps of a mixed batch from an
+ * action sequence — bioim_rollout for the handles of bioim_step_group.  The
+ * buffers are that call's padded full-batch ones (all handles on one device,
+ * same precision and I/O strides): handle i owns rows [sum(n_<i), sum(n_<=i))
+ * of every step's slice, N is the sum of the handles' env counts:
+ *   actions: step k reads [N][act_stride] at actions + k * action_step_stride
+ *     elements; a stride of 0 repeats the same actions every step;
+ *   reward_seq [steps][N] (may be NULL); done_seq [steps][N] (required);
+ *   obs_seq (may be NULL) [steps][N][obs_stride];
+ *   obs_last (may be NULL) [N][obs_stride]: the last step's rows only;
+ *   info_seq (may be NULL) [steps][N][info_stride].
+ * State and every output are bit for bit those of `steps` bioim_step_group
+ * calls on the same slices: in-kernel auto-resets (reset-table rows, reset
+ * counters), the realize cache, each handle's active mask and final_obs.
+ * Columns past a handle's own row widths are not written.
+ * stop_at_done (auto-reset off in every handle) works as in bioim_rollout,
+ * per env; each handle's caller mask is read, never written (the call keeps
+ * its own mask per handle).
+ * Asynchronous on hs[0]'s stream; only the one-time reset-table builds and
+ * the first stop_at_done call's allocation of a handle's mask synchronize
+ * (an RK handle's check for suspended envs waits for its stream).
+ * Paths: where bioim_step_group would fuse (nh == 2, group fusion on, fp64,
+ * a fused topology pair, no push table, semi-implicit) and neither handle
+ * has a force report or state storage, the whole call is ONE launch of the
+ * two-topology rollout kernel (the workgroups of one segment first, then the
+ * other's; the per-step pitch of the sequence buffers is N rows), and
+ * bioim_rollout_group_fused returns 1.  Every other case loops from C over
+ * what bioim_step_group enqueues per step — the fused step launch where
+ * eligible, else one launch per segment, forked and joined — followed, with
+ * stop_at_done, by the per-segment freeze launches on hs[0]'s stream; results
+ * identical, bioim_rollout_group_fused returns 0.  bioim_group_fused's answer
+ * is left as it was.  nh == 1 behaves as bioim_rollout.
+ * Refused with BIOIM_E_ARG and a message starting "bioim_rollout_group:"
+ * before any device call: null hs, nh <= 0 or a null handle in the list, null
+ * actions or done_seq, steps <= 0, a negative stride, handles differing in
+ * device, precision or I/O strides, any budgeted RK handle (rk_budget > 0) or
+ * one with suspended envs, stop_at_done with auto-reset on in any handle.
+ * The buffers' sizes are the caller's contract (MixedVectorEnv.rollout checks
+ * them).  No reference counterpart (one OsimModel steps one env from Python;
+ * the mixed batch is this project's). */
+int bioim_rollout_group(bioim_handle_t **hs, int nh, const void *actions, int steps, int64_t action_step_stride,
+                        void *obs_seq, void *obs_last, void *reward_seq, uint8_t *done_seq, void *info_seq,
+                        int stop_at_done);
+/* 1 if the last bioim_rollout_group with h as its first handle ran as one
+ * launch of the two-topology rollout kernel (nh == 1: of the rollout kernel),
+ * 0 if it looped over the step kernels (or none ran yet); -1 for a null
+ * handle. */
+int bioim_rollout_group_fused(const bioim_handle_t *h);
 
 /* Integrator of the physics between env steps.  kind 0: the fixed
  * semi-implicit substeps (the pack's nsub; default).  kind 1: the reference's
