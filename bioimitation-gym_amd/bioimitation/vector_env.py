@@ -494,6 +494,25 @@ class VectorEnv:
             _lib.check(self._L.bioim_copy_state_rows(self._h, self._ptr(ids), n, self._ptr(out)))
         return out
 
+    def muscle_analysis(self, env_ids=None, want=('length', 'speed', 'dldq'), rows=None):
+        """Muscle analysis (``bioimitation.muscle_analysis``) at the envs'
+        current state: {key: device tensor} for the keys of ``want``, one row
+        per env (or per listed env, in the list's order).  q, u, activations
+        and fiber lengths are gathered on the device (``state_rows``) and go
+        to one ``bioim_muscle_eval`` launch on the env's stream: no host round
+        trip, no synchronization, and the envs are only read.  ``rows``: state
+        rows already gathered for these envs (``state_rows``' result), to
+        spare the gather."""
+        from . import muscle_analysis as ma
+        from .packdef import state_row_slices
+        pk = self.pack
+        if rows is None:
+            rows = self.state_rows(env_ids=env_ids)
+        sl, _ = state_row_slices(pk.ndof, pk.nmuscle, pk.nact, pk.horizon)
+        q, u, act, lce = (rows[:, sl[f]].to(self.dtype).contiguous() for f in ('q', 'u', 'act', 'lce'))
+        _, want = ma.check_args(pk.ndof, pk.nmuscle, q, u, act, lce, want)
+        return ma.launch(self, q, u, act, lce, want)
+
     def load_state(self, rows, env_ids=None):
         """Write flat state rows (``state_rows``' layout: a contiguous
         (n, state_dim) float64 tensor on the env's device) into the listed

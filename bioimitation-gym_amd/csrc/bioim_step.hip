@@ -2530,6 +2530,129 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) void id_kernel(IdArgs<T, Real> a)
     if (lane < ND) GAT(a.out, (size_t)idx * ND + lane, (size_t)a.n * ND) = r;
 }
 
+/* -------------------------------------------------------- muscle analysis
+ * bioim_muscle_eval (include/bioim.h): the muscles' geometry, fiber state
+ * and generalized force at n arbitrary states.  One state per G lanes, the
+ * env kernel's LDS image and kinematics (as id_kernel, without the inertia
+ * half); then lane l takes the muscles of slots l, l + G, ... (mslot, the
+ * step's own assignment) and runs the step's device functions on them, with
+ * the step's branch-free switches: muscle_path, then muscle_equilibrium where
+ * no fiber length is given, then muscle_eval at excitation = activation and a
+ * cold fiber-velocity start.  -F_t dL/dq goes to the step's TAU slots and the
+ * dof lanes gather it through SM.tau_src in the step's order.  Nothing of the
+ * env state is read or written.  Any output may be null. */
+template <class T, typename Real> struct MaArgs {
+    const DModel<Real> *Mg;
+    const SModel<T, Real> *Sg;
+    int n;
+    const Real *q, *u, *act, *lce;
+    Real *length, *speed, *dldq, *fiber, *tau;
+};
+
+template <class T, typename Real>
+__global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_eu(1, 1))) void ma_kernel(MaArgs<T, Real> a) {
+    using LY = Lay<T, Real>;
+    constexpr int G = T::G, ND = LY::ND, NB = T::NB, NM = T::NM, MPL = LY::MPL, NSP = T::MAXSPAN, EPB = BIOIM_EPB;
+    constexpr size_t SMB = smodel_bytes<T, Real>();
+    static_assert(NM > 0, "muscle topologies only");
+    /* the step's switches (dynamics(), semi-implicit kernels) */
+    constexpr bool BFK = T::PLANAR || BIOIM_BF_SPATIAL, BF3 = !T::PLANAR;
+    constexpr bool BFK_FN = BFK || (BF3 && (BIOIM_BF3 & 1)), BFK_PATH = BFK || (BF3 && (BIOIM_BF3 & 2));
+    constexpr bool BFK_EQ = BFK || (BF3 && (BIOIM_BF3 & 16)), BFK_ME = BFK || (BF3 && (BIOIM_BF3 & 128));
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    {
+        const uint4 *src = reinterpret_cast<const uint4 *>(a.Sg);
+        uint4 *dst = reinterpret_cast<uint4 *>(smem_raw);
+        for (int i = threadIdx.x; i < (int)(SMB / 16); i += BIOIM_EPB * G) dst[i] = src[i];
+    }
+    __syncthreads();
+    const SModel<T, Real> &SM = *reinterpret_cast<const SModel<T, Real> *>(smem_raw);
+    const DModel<Real> &M = *a.Mg;
+    const int lane = threadIdx.x % G, slot = threadIdx.x / G;
+    const int idx = blockIdx.x * EPB + slot;
+    if (idx >= a.n) return;
+    Real *lds = reinterpret_cast<Real *>(smem_raw + SMB) + slot * LY::SIZE;
+    Real qd = 0, ud = 0;
+    if (lane < ND) {
+        qd = GAT(a.q, (size_t)idx * ND + lane, (size_t)a.n * ND);
+        ud = a.u ? GAT(a.u, (size_t)idx * ND + lane, (size_t)a.n * ND) : Real(0);
+    }
+    publish_coords<T, Real>(M, SM, lds, lane, qd, ud);
+    if (lane < ND) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) lds[LY::SL + 6 * lane + i] = 0;
+    }
+    wave_sync();
+    Real x0 = 0;
+    if constexpr (T::TX >= 0) {
+        if constexpr (T::coord_dof[T::TX] >= 0) x0 = M.float_origin ? lds[LY::QF + T::TX] : Real(0);
+    }
+    fn_slots<BFK_FN, T, Real>(SM, lds, lane);
+    if (lane < NB) kin_local<T, Real>(SM, lds, lane);
+    if (lane == NB) kin_ground<T, Real>(lds, x0);
+    wave_sync();
+    if (lane < NB) kin_chain<T, Real>(SM, lds, lane, x0);
+    wave_sync();
+    if (lane < ND) kin_column<T, Real>(SM, lds, lane);
+    wave_sync();   /* the columns are out, and the joint-local region (LOC / SL) the TAU slots share is free */
+    const bool fib = a.act != nullptr;
+    if (lane == 0) lds[LY::TAU + LY::TZ] = Real(0);
+    sfor<0, MPL>([&](auto jI) {
+        constexpr int j = decltype(jI)::value;
+        const int m = mslot<T>(lane + j * G);
+        if (m < NM) {
+            const SMuscle<Real> &mu = SM.mus[m];
+            const size_t row = (size_t)idx * NM + m, rows = (size_t)a.n * NM;
+            Real L, dLs[NSP];
+            muscle_path<BFK_PATH, T, Real>(SM, mu, lds, L, dLs);
+            if (a.length) GAT(a.length, row, rows) = L;
+            if (a.speed) {
+                Real s = 0;
+#pragma unroll
+                for (int k = 0; k < NSP; ++k) {
+                    const int dk = k < mu.nspan ? mu.span[k] : 0;
+                    const Real uk = lds[LY::UF + SM.dof_coord[dk]];
+                    s += k < mu.nspan ? dLs[k] * uk : Real(0);
+                }
+                GAT(a.speed, row, rows) = s;
+            }
+            if (a.dldq) {
+                /* the whole row: the span's entries, exact zeros elsewhere */
+#pragma unroll
+                for (int d = 0; d < ND; ++d) {
+                    Real v = 0;
+#pragma unroll
+                    for (int k = 0; k < NSP; ++k) v = (k < mu.nspan && mu.span[k] == d) ? dLs[k] : v;
+                    GAT(a.dldq, row * ND + d, rows * ND) = v;
+                }
+            }
+            if (fib) {
+                const Real a_ = GAT(a.act, row, rows);
+                Real l_;
+                if (a.lce) l_ = GAT(a.lce, row, rows);
+                else l_ = muscle_equilibrium<BFK_EQ, T, Real>(SM, mu, a_, L);
+                MState<Real> ms;
+                muscle_eval<BFK_ME, true, T, Real>(SM, mu, a_, l_, a_, L, Real(0), ms);
+                if (a.fiber) {
+                    Real *f = a.fiber + GIDX(row * BIOIM_MUSCLE_FIBER_DIM, rows * BIOIM_MUSCLE_FIBER_DIM);
+                    f[0] = ms.lce; f[1] = ms.vce; f[2] = ms.Ft; f[3] = ms.Ff; f[4] = ms.Fa;
+                }
+                const Real nFt = -ms.Ft;
+                Real *ts = lds + LY::TAU + (lane + j * G) * NSP;
+#pragma unroll
+                for (int k = 0; k < NSP; ++k) ts[k] = nFt * dLs[k];
+            }
+        }
+    });
+    wave_sync();
+    if (fib && a.tau && lane < ND) {
+        Real r = 0;
+#pragma unroll
+        for (int i = 0; i < T::MAXARM; ++i) r += lds[LY::TAU + SM.tau_src[lane][i]];
+        GAT(a.tau, (size_t)idx * ND + lane, (size_t)a.n * ND) = r;
+    }
+}
+
 /* ---------------------------------------------------------------- kernel
  * Launch arguments of one env segment (one handle).  mode 0: env step
  * (optionally with in-kernel auto-reset); mode 1: reset the listed envs.
@@ -4373,6 +4496,12 @@ struct RolloutCall {   /* bioim_rollout's arguments (untyped), for Ops::rollout 
     int stop_at_done;
 };
 
+struct MuscleEvalCall {   /* bioim_muscle_eval's arguments (untyped), for Ops::ma_launch */
+    int n;
+    const void *q, *u, *act, *lce;
+    void *length, *speed, *dldq, *fiber, *tau;
+};
+
 struct Ops {
     const char *topo;   /* the topology struct's name (fused-pair lookup) */
     int lanes;
@@ -4382,6 +4511,8 @@ struct Ops {
     void (*launch)(bioim_handle_t *, int mode, const void *actions, void *obs, void *reward, uint8_t *done, void *info,
                    const int32_t *env_ids, const int32_t *ref_index, int n_list, const OsimCall *oc);
     void (*id_launch)(bioim_handle_t *, int op, int n, const void *q, const void *u, const void *v, void *out);
+    /* bioim_muscle_eval's launcher; null for a torque topology (no muscles, no kernel) */
+    void (*ma_launch)(bioim_handle_t *, const MuscleEvalCall &);
     /* the fused rollout kernel's launcher; null where that instantiation is
      * left out (bioim_rollout then loops over `launch`) */
     void (*rollout)(bioim_handle_t *, const RolloutCall &);
@@ -4643,6 +4774,21 @@ void id_launch_impl(bioim_handle_t *h, int op, int n, const void *q, const void 
     hipLaunchKernelGGL((id_kernel<T, Real>), dim3((n + EPB - 1) / EPB), dim3(BIOIM_EPB * T::G), lds, h->stream, a);
 }
 
+template <class T, typename Real> void ma_launch_impl(bioim_handle_t *h, const MuscleEvalCall &c) {
+    constexpr int EPB = BIOIM_EPB;
+    MaArgs<T, Real> a;
+    a.Mg = reinterpret_cast<const DModel<Real> *>(h->model);
+    a.Sg = reinterpret_cast<const SModel<T, Real> *>(h->smodel);
+    a.n = c.n;
+    a.q = reinterpret_cast<const Real *>(c.q); a.u = reinterpret_cast<const Real *>(c.u);
+    a.act = reinterpret_cast<const Real *>(c.act); a.lce = reinterpret_cast<const Real *>(c.lce);
+    a.length = reinterpret_cast<Real *>(c.length); a.speed = reinterpret_cast<Real *>(c.speed);
+    a.dldq = reinterpret_cast<Real *>(c.dldq); a.fiber = reinterpret_cast<Real *>(c.fiber);
+    a.tau = reinterpret_cast<Real *>(c.tau);
+    constexpr size_t lds = lds_bytes<T, Real, false>();
+    hipLaunchKernelGGL((ma_kernel<T, Real>), dim3((c.n + EPB - 1) / EPB), dim3(BIOIM_EPB * T::G), lds, h->stream, a);
+}
+
 template <class T, typename Real> int upload_smodel(bioim_handle_t *h) {
     static_assert(lds_bytes<T, Real, true>() <= 163840, "LDS image + env regions exceed 160 KiB");
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&env_kernel<T, Real, false, false>),
@@ -4665,6 +4811,9 @@ template <class T, typename Real> int upload_smodel(bioim_handle_t *h) {
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, Real, false>()));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&rollout_kernel<T, Real>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, Real, false>()));
+    if constexpr (T::NM > 0)
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&ma_kernel<T, Real>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, Real, false>()));
     constexpr size_t B = smodel_bytes<T, Real>();
     std::vector<unsigned char> img(B, 0);
     build_smodel<T, Real>(h->pack, *reinterpret_cast<SModel<T, Real> *>(img.data()));
@@ -4680,6 +4829,11 @@ template <class T> bool pick(const bioim_modelpack_t &p, int precision, Ops &ops
     ops.topo = name;
     ops.lanes = T::G;
     ops.cache_dim = CacheLay<T>::DIM;
+    ops.ma_launch = nullptr;
+    if constexpr (T::NM > 0) {
+        if (precision == 64) ops.ma_launch = &ma_launch_impl<T, double>;
+        else ops.ma_launch = &ma_launch_impl<T, float>;
+    }
     if (precision == 64) {
         ops.launch = &launch_impl<T, double>;
         ops.id_launch = &id_launch_impl<T, double>;
@@ -5364,6 +5518,22 @@ int bioim_id_eval(bioim_handle_t *h, int op, int n, const void *q, const void *u
     if (n == 0) return 0;
     HIPCHK(hipSetDevice(h->device));
     h->ops.id_launch(h, op, n, q, u, v, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int bioim_muscle_eval(bioim_handle_t *h, int n, const void *q, const void *u, const void *act, const void *lce,
+                      void *length, void *speed, void *dldq, void *fiber, void *tau) {
+    if (!h) return fail(BIOIM_E_ARG, "bioim_muscle_eval: null handle");
+    if (n < 0) return fail(BIOIM_E_ARG, "bioim_muscle_eval: negative n");
+    if (n > 0 && !q) return fail(BIOIM_E_ARG, "bioim_muscle_eval: null q");
+    if (!length && !speed && !dldq && !fiber && !tau) return fail(BIOIM_E_ARG, "bioim_muscle_eval: no output requested");
+    if ((fiber || tau) && !act) return fail(BIOIM_E_ARG, "bioim_muscle_eval: fiber and tau need act");
+    if (h->nmuscle <= 0 || !h->ops.ma_launch) return fail(BIOIM_E_ARG, "bioim_muscle_eval: the model has no muscles");
+    if (n == 0) return 0;
+    HIPCHK(hipSetDevice(h->device));
+    const MuscleEvalCall c{n, q, u, act, lce, length, speed, dldq, fiber, tau};
+    h->ops.ma_launch(h, c);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -156,6 +156,34 @@ enum {
     BIOIM_ID_TOTAL = 5,
 };
 int bioim_id_eval(bioim_handle_t *h, int op, int n, const void *q, const void *u, const void *v, void *out);
+/* Muscle analysis (OpenSim's MuscleAnalysis next to InverseDynamics) on the
+ * handle's model, batched over n arbitrary states — not the handle's envs:
+ * the env state and the realize cache are neither read nor written.  All
+ * pointers are device pointers in the handle's precision, dof order as for
+ * bioim_id_eval; any output may be NULL.
+ *   length [n][nmuscle]        musculotendon path length L;
+ *   speed  [n][nmuscle]        dL/dt = sum_d dL/dq_d u_d (u NULL: u = 0);
+ *   dldq   [n][nmuscle][ndof]  dL/dq over every dof: exact zeros outside the
+ *     muscle's span and on the floating-base dofs (their sum over a path is
+ *     zero).  OpenSim's moment arm is -dL/dq;
+ *   fiber  [n][nmuscle][BIOIM_MUSCLE_FIBER_DIM]  fiber length, fiber velocity
+ *     (m/s), tendon force, fiber force, active fiber force: the values the
+ *     step's muscle evaluation forms at (act, lce, L), the excitation taken
+ *     equal to act and the fiber-velocity solve started cold.  lce NULL: each
+ *     fiber length is first set to its static equilibrium at (act, L)
+ *     (equilibrateMuscles); a given lce is clamped at the muscle's minimum
+ *     fiber length as in the step;
+ *   tau    [n][ndof]           the muscles' generalized force,
+ *     tau_d = -sum_m dL_m/dq_d Ft_m.
+ * fiber and tau need act ([n][nmuscle]).  BIOIM_E_ARG, before any device
+ * call, for: a null handle, n < 0, null q with n > 0, every output NULL, fiber
+ * or tau without act, a model without muscles.  n == 0 returns BIOIM_OK
+ * without a launch.  Asynchronous on the handle's stream; synchronizes
+ * nothing.  No reference counterpart (the reference reaches these values one
+ * OpenSim state at a time, through OsimModel). */
+#define BIOIM_MUSCLE_FIBER_DIM 5
+int bioim_muscle_eval(bioim_handle_t *h, int n, const void *q, const void *u, const void *act, const void *lce,
+                      void *length, void *speed, void *dldq, void *fiber, void *tau);
 /* OsimModel calls on single envs (the reference's physics facade,
  * opensim_wrapper.py:92-332), for callers that drive the model directly
  * (tests/example_position_control.py:203-223; the env methods
