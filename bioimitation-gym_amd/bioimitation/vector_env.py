@@ -513,6 +513,29 @@ class VectorEnv:
         _, want = ma.check_args(pk.ndof, pk.nmuscle, q, u, act, lce, want)
         return ma.launch(self, q, u, act, lce, want)
 
+    def static_optimization(self, qdd=None, tau=None, env_ids=None, reserve=1.0, lo=0.0, hi=1.0, passive=False,
+                            want=('act',), rows=None):
+        """Static optimization (``bioimitation.static_optimization``) at the
+        envs' current q and u: the activations that produce the target
+        generalized force at least effort, one row per env (or per listed
+        env, in the list's order).  Exactly one of ``qdd`` (accelerations; the
+        target is then their inverse-dynamics residual) and ``tau`` (the
+        target itself), ``[rows][ndof]``.  q and u are gathered on the device
+        (``state_rows``) and go to the launches on the env's stream: no host
+        round trip, no synchronization, and the envs are only read.  Muscle
+        envs in fp64 only (``ValueError`` otherwise).  ``rows``: state rows
+        already gathered for these envs, to spare the gather."""
+        from . import static_optimization as so
+        from .packdef import state_row_slices
+        pk = self.pack
+        so.check_env(self)
+        if rows is None:
+            rows = self.state_rows(env_ids=env_ids)
+        sl, _ = state_row_slices(pk.ndof, pk.nmuscle, pk.nact, pk.horizon)
+        q, u = (rows[:, sl[f]].contiguous() for f in ('q', 'u'))
+        _, want, lam = so.check_args(pk.ndof, pk.nmuscle, q, u, qdd, tau, reserve, lo, hi, want)
+        return so.solve_on(self, q, u, qdd, tau, lam, lo, hi, passive, want)
+
     def load_state(self, rows, env_ids=None):
         """Write flat state rows (``state_rows``' layout: a contiguous
         (n, state_dim) float64 tensor on the env's device) into the listed

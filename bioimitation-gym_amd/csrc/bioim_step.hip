@@ -2653,6 +2653,480 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_e
     }
 }
 
+/* ----------------------------------------------------- static optimization
+ * bioim_static_opt (include/bioim.h): per state the muscle activations that
+ * produce a target generalized force at least effort,
+ *     min sum_m a_m^2 + sum_d lam_d (tau_d - (B a + c)_d)^2,  lo <= a_m <= hi,
+ * B[d][m] = -dL_m/dq_d Fa_m, c_d = -sum_m dL_m/dq_d Fp_m (0: passive off), Fa /
+ * Fp the rigid-tendon capacities of muscle_rigid_capacity.  fp64 only.
+ *
+ * ma_kernel's launch shape and prologue (one state per G lanes, the model
+ * image in LDS, kinematics without inertias or contact).  The QP's variable s
+ * is the muscle of lane slot s (mslot: a bijection of [0, NM)), so lane l owns
+ * the variables l, l + G.  The muscle rounds leave per slot the B entries over
+ * the muscle's span (the step's TAU slots, gathered per dof through
+ * SM.tau_src) and, behind them, the passive entries -dL/dq Fp.  After them the
+ * frames and columns are dead and [0, Lay::U) of the state's LDS region takes
+ * the solver's data (SoLay).
+ *
+ * Solver: a primal active set (BVLS).  All variables start at lo.  Per pass
+ * the dof lanes form the residual rho = tau - c - B a in dof space and the
+ * muscle lanes the negative gradient w = B^T lam rho - a from it (the
+ * normal-equations right-hand side g - H a loses cond(H) ~ 1e5 digits of a
+ * large tau; this form loses them of the small residual only).  A pass in
+ * CHECK mode frees the bound variable whose w points furthest inward (ties:
+ * the lowest muscle index; w must exceed 16 ulp of the sums that form it, rho's
+ * cancellation included), or ends: the KKT conditions hold.  Every pass not
+ * ended then solves H_FF dz = w_F over the free set by a Cholesky
+ * factorization of H with the bound rows and columns replaced by the
+ * identity (fixed size NM, no index sets), the right-hand side carried as row
+ * NM of the packed matrix; a full step that stays inside the box is taken
+ * and the pass after it checks again, otherwise the step stops at the first
+ * bound met (ties: the lowest muscle index), that variable is bound, and the
+ * next pass solves again.  A variable freed by rounding noise (its step leads
+ * straight back out) is bound again and kept out of the choice until a full
+ * step succeeds.  Each pass costs one factorization; the count of them is
+ * the state's status.  SoLay::CAP passes end the loop with status -1, a
+ * pivot <= 0 (or NaN) with -2.
+ *
+ * The 4 states of a wave need different pass counts: every lane loops under
+ * its own state's done flag (uniform over the state's G lanes) and the wave
+ * leaves when all are done; only wave_sync orders the LDS traffic, and no
+ * workgroup barrier follows the idx >= n exit.  No atomics, no read-modify-
+ * write at run-time indices shared between lanes, sums in a fixed order: a
+ * state's result does not depend on n or its neighbours.  Matrices, sets and
+ * flags live in LDS; the per-lane arrays have compile-time indices only. */
+template <int G, typename V> DEV V group_min(V x) {
+#pragma unroll
+    for (int off = G / 2; off >= 1; off >>= 1) {
+        const V y = __shfl_xor(x, off, G);
+        x = y < x ? y : x;
+    }
+    return x;
+}
+
+template <class T, typename Real> struct SoArgs {
+    const DModel<Real> *Mg;
+    const SModel<T, Real> *Sg;
+    int n, passive;
+    const Real *q, *u, *tau, *row_weight;
+    Real lo, hi;
+    Real *act, *residual, *tau_muscle, *capacity;
+    int32_t *status;
+};
+
+/* the solver's map of [0, Lay::U) (reals), and the slot arrays behind it */
+template <class T, typename Real> struct SoLay {
+    using LY = Lay<T, Real>;
+    static constexpr int NM = T::NM > 0 ? T::NM : 1, ND = LY::ND, NSP = T::MAXSPAN;
+    static constexpr int NH = NM * (NM + 1) / 2;
+    static constexpr int H = 0;                /* [NH] packed lower H = I + B^T lam B                    */
+    static constexpr int A = H + NH;           /* [NH + NM] the masked copy, then its factor; row NM: rhs */
+    static constexpr int DSP = A;              /* assembly only: [NM][NSP] dof of each B entry (-1: none) */
+    static constexpr int D = A + NH + NM;      /* [NM] reciprocal pivots                                  */
+    static constexpr int X = D + NM;           /* [NM] the activations                                    */
+    static constexpr int Z = X + NM;           /* [NM] the step dz                                        */
+    static constexpr int F = Z + NM;           /* [NM] -1 at lo, +1 at hi, 0 free                         */
+    static constexpr int RHO = F + NM;         /* [ND] lam_d rho_d                                        */
+    static constexpr int RER = RHO + ND;       /* [ND] lam_d (|tau_d - c_d| + sum |B a|): rho's rounding scale */
+    static constexpr int END = RER + ND;
+    static constexpr int BS = LY::TAU;         /* [MPL G][NSP] + zero slot: B entries by lane slot        */
+    static constexpr int CS = BS + LY::TAUN;   /* the same for -dL/dq Fp                                  */
+    static constexpr int CAP = 8 * NM;         /* passes; the most observed: 21 (NM = 14), 29 (NM = 22), 18 (NM = 19) */
+    static_assert(END <= LY::U, "the solver's data must fit below the union region");
+    static_assert(NM * NSP <= NH + NM, "the dof table must fit in the work matrix");
+    static_assert(CS + LY::TAUN <= LY::SIZE0, "two slot arrays must fit in the union region");
+};
+
+/* Rigid-tendon capacity of one muscle at path length L and lengthening speed
+ * Ld (OpenSim's StaticOptimization assumptions): Fa the active fiber force
+ * along the tendon at activation 1, Fp the passive one.
+ *   w = l_opt sin(alpha_opt), l_t = max(L - l_ts, 0),
+ *   l_m = max(sqrt(l_t^2 + w^2), l_min), cos = sqrt(l_m^2 - w^2) / l_m,
+ *   Fa = F0 fal(l_m / l_opt) fv(Ld cos / (l_opt v_max)) cos,
+ *   Fp = F0 fpe(l_m / l_opt) cos,  both cut at 0 from below */
+template <class T, typename Real>
+DEV void muscle_rigid_capacity(const SModel<T, Real> &SM, const SMuscle<Real> &mu, Real L, Real Ld, Real &Fa, Real &Fp) {
+    const DCurve<Real> &Cfal = SM.curve[mu.cv[0]], &Cfv = SM.curve[mu.cv[1]], &Cfpe = SM.curve[mu.cv[2]];
+    const Real w = mu.width, lmin = mu.lmin, zero = 0;
+    Real lt = L - mu.lts;
+    lt = lt > zero ? lt : zero;
+    Real lm = sqrt(lt * lt + w * w);
+    lm = lm > lmin ? lm : lmin;
+    const Real cosa = sqrt(lm * lm - w * w) / lm;
+    Real fal, fv, fpe, d;
+    curve_eval<true>(Cfal, lm / mu.lopt, fal, d);
+    curve_eval<true>(Cfv, Ld * cosa / mu.lv, fv, d);
+    curve_eval<true>(Cfpe, lm / mu.lopt, fpe, d);
+    Fa = mu.fiso * fal * fv * cosa;
+    Fp = mu.fiso * fpe * cosa;
+    /* a curve whose minimum is exactly 0 (the palsy model's fal) comes out of
+     * the power-basis Horner form as -1e-32 at its first node; a capacity is
+     * not negative, and a muscle without one must have B = 0 exactly */
+    const Real zero_f = 0;
+    Fa = Fa > zero_f ? Fa : zero_f;
+    Fp = Fp > zero_f ? Fp : zero_f;
+}
+
+template <class T, typename Real>
+__global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_eu(1, 1))) void so_kernel(SoArgs<T, Real> a) {
+    using LY = Lay<T, Real>;
+    using SL = SoLay<T, Real>;
+    constexpr int G = T::G, ND = LY::ND, NB = T::NB, NM = T::NM, MPL = LY::MPL, NSP = T::MAXSPAN, EPB = BIOIM_EPB;
+    constexpr int NH = SL::NH;
+    constexpr size_t SMB = smodel_bytes<T, Real>();
+    static_assert(NM > 0, "muscle topologies only");
+    constexpr bool BFK = T::PLANAR || BIOIM_BF_SPATIAL, BF3 = !T::PLANAR;
+    constexpr bool BFK_FN = BFK || (BF3 && (BIOIM_BF3 & 1)), BFK_PATH = BFK || (BF3 && (BIOIM_BF3 & 2));
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    {
+        const uint4 *src = reinterpret_cast<const uint4 *>(a.Sg);
+        uint4 *dst = reinterpret_cast<uint4 *>(smem_raw);
+        for (int i = threadIdx.x; i < (int)(SMB / 16); i += BIOIM_EPB * G) dst[i] = src[i];
+    }
+    __syncthreads();
+    const SModel<T, Real> &SM = *reinterpret_cast<const SModel<T, Real> *>(smem_raw);
+    const DModel<Real> &M = *a.Mg;
+    const int lane = threadIdx.x % G, slot = threadIdx.x / G;
+    const int idx = blockIdx.x * EPB + slot;
+    if (idx >= a.n) return;
+    Real *lds = reinterpret_cast<Real *>(smem_raw + SMB) + slot * LY::SIZE;
+    Real qd = 0, ud = 0;
+    if (lane < ND) {
+        qd = GAT(a.q, (size_t)idx * ND + lane, (size_t)a.n * ND);
+        ud = a.u ? GAT(a.u, (size_t)idx * ND + lane, (size_t)a.n * ND) : Real(0);
+    }
+    publish_coords<T, Real>(M, SM, lds, lane, qd, ud);
+    if (lane < ND) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) lds[LY::SL + 6 * lane + i] = 0;
+    }
+    wave_sync();
+    Real x0 = 0;
+    if constexpr (T::TX >= 0) {
+        if constexpr (T::coord_dof[T::TX] >= 0) x0 = M.float_origin ? lds[LY::QF + T::TX] : Real(0);
+    }
+    fn_slots<BFK_FN, T, Real>(SM, lds, lane);
+    if (lane < NB) kin_local<T, Real>(SM, lds, lane);
+    if (lane == NB) kin_ground<T, Real>(lds, x0);
+    wave_sync();
+    if (lane < NB) kin_chain<T, Real>(SM, lds, lane, x0);
+    wave_sync();
+    if (lane < ND) kin_column<T, Real>(SM, lds, lane);
+    wave_sync();   /* the columns are out, and the joint-local region (LOC / SL) the slot arrays share is free */
+    const bool passive = a.passive != 0;
+    const Real lo = a.lo, hi = a.hi;
+    if (lane == 0) {
+        lds[SL::BS + LY::TZ] = Real(0);
+        lds[SL::CS + LY::TZ] = Real(0);
+    }
+    /* muscle rounds: capacity, then the B (and passive) entries of the slot */
+    int mi[MPL];     /* the slot's muscle (NM: none) */
+    sfor<0, MPL>([&](auto jI) {
+        constexpr int j = decltype(jI)::value;
+        const int s = lane + j * G;
+        const int m = mslot<T>(s);
+        mi[j] = m < NM ? m : NM;
+        Real *bs = lds + SL::BS + s * NSP, *cs = lds + SL::CS + s * NSP;
+        if (m < NM) {
+            const SMuscle<Real> &mu = SM.mus[m];
+            Real L, dLs[NSP];
+            muscle_path<BFK_PATH, T, Real>(SM, mu, lds, L, dLs);
+            /* a dof that moves every point of the path moves it rigidly: dL/dq is
+             * exactly 0 there (the sum over the path vanishes, as on the floating
+             * base, which the span leaves out for that reason), unless a moving
+             * point's own coordinate is that dof.  muscle_path's sum leaves
+             * rounding noise (1e-15), which Fa ~ 1e4 N and a joint residual ~ 1e3
+             * N m turn into activations of 1e-8 for a muscle without any moment
+             * arm: such span entries are set to the 0 they stand for */
+            unsigned common = ~0u, mov = 0u;
+#pragma unroll
+            for (int p = 0; p < T::MAXPT; ++p) {
+                const DPathPt<Real> &pt = SM.pt[mu.pt_off + (p < mu.npt ? p : 0)];
+                common &= pt.dofmask;
+                mov |= (p < mu.npt && pt.mdof >= 0) ? 1u << pt.mdof : 0u;
+            }
+            const unsigned rigid = common & ~mov;
+            Real Ld = 0;
+#pragma unroll
+            for (int k = 0; k < NSP; ++k) {
+                const int dk = k < mu.nspan ? mu.span[k] : 0;
+                dLs[k] = ((rigid >> dk) & 1u) ? Real(0) : dLs[k];
+                const Real uk = lds[LY::UF + SM.dof_coord[dk]];
+                Ld += k < mu.nspan ? dLs[k] * uk : Real(0);
+            }
+            Real Fa, Fp;
+            muscle_rigid_capacity<T, Real>(SM, mu, L, Ld, Fa, Fp);
+            if (a.capacity) {
+                const size_t row = (size_t)idx * NM + m, rows = (size_t)a.n * NM;
+                Real *cp = a.capacity + GIDX(row * 2, rows * 2);
+                cp[0] = Fa; cp[1] = Fp;
+            }
+#pragma unroll
+            for (int k = 0; k < NSP; ++k) {
+                const bool in = k < mu.nspan;
+                bs[k] = in ? -dLs[k] * Fa : Real(0);
+                cs[k] = (in && passive) ? -dLs[k] * Fp : Real(0);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < NSP; ++k) { bs[k] = Real(0); cs[k] = Real(0); }
+        }
+    });
+    wave_sync();   /* frames, columns, coordinates are dead: [0, U) is the solver's */
+    /* dof lanes: row weight, target minus passive force */
+    Real lam = 0, tq = 0, cq = 0, tc = 0;
+    if (lane < ND) {
+        lam = a.row_weight ? a.row_weight[lane] : Real(1);
+        tq = GAT(a.tau, (size_t)idx * ND + lane, (size_t)a.n * ND);
+#pragma unroll
+        for (int i = 0; i < T::MAXARM; ++i) cq += lds[SL::CS + SM.tau_src[lane][i]];
+        tc = tq - cq;
+    }
+    /* muscle lanes: the variables start at lo; the dof table of the B entries;
+     * own entries and dofs to registers */
+    Real xv[MPL], fl[MPL], bown[MPL][NSP];
+    int down[MPL][NSP];
+    bool blk[MPL];
+    sfor<0, MPL>([&](auto jI) {
+        constexpr int j = decltype(jI)::value;
+        const int s = lane + j * G;
+        xv[j] = lo; fl[j] = Real(-1); blk[j] = false;
+        const SMuscle<Real> &mu = SM.mus[mi[j] < NM ? mi[j] : 0];
+#pragma unroll
+        for (int k = 0; k < NSP; ++k) {
+            const bool in = mi[j] < NM && k < mu.nspan;
+            down[j][k] = in ? mu.span[k] : -1;
+            bown[j][k] = lds[SL::BS + s * NSP + k];
+            if (s < NM) lds[SL::DSP + s * NSP + k] = Real(down[j][k]);
+        }
+        if (s < NM) { lds[SL::X + s] = lo; lds[SL::F + s] = Real(-1); }
+    });
+    if (lane < ND) lds[SL::RHO + lane] = lam;   /* lam_d, for the assembly (RHO is rewritten per pass) */
+    wave_sync();
+    /* H: row s (uniform), the lane's columns t <= s */
+    for (int s = 0; s < NM; ++s) {
+        Real ws[NSP], dsr[NSP];
+#pragma unroll
+        for (int k = 0; k < NSP; ++k) {
+            dsr[k] = lds[SL::DSP + s * NSP + k];
+            const int dk = dsr[k] >= Real(0) ? (int)dsr[k] : 0;
+            ws[k] = lds[SL::RHO + dk] * lds[SL::BS + s * NSP + k];   /* lam_d B_ds (0 for an unused entry) */
+        }
+        sfor<0, MPL>([&](auto jI) {
+            constexpr int j = decltype(jI)::value;
+            const int t = lane + j * G;
+            if (t <= s) {
+                Real acc = t == s ? Real(1) : Real(0);
+#pragma unroll
+                for (int k = 0; k < NSP; ++k)
+#pragma unroll
+                    for (int kk = 0; kk < NSP; ++kk)
+                        acc += (dsr[k] == Real(down[j][kk]) && down[j][kk] >= 0) ? ws[k] * bown[j][kk] : Real(0);
+                lds[SL::H + s * (s + 1) / 2 + t] = acc;
+            }
+        });
+    }
+    wave_sync();   /* the dof table is dead: its place is the work matrix */
+    const Real tiny = Real(16) * Real(2.220446049250313e-16);   /* 16 ulp of the sums that form w */
+    int status = 0, it = 0, mode = 0, tnew = -1;
+    bool done = false;
+    while (!done) {
+        /* rho and its rounding scale (dof lanes), then w (muscle lanes) */
+        if (lane < ND) {
+            Real sum = 0, asum = 0;
+#pragma unroll
+            for (int i = 0; i < T::MAXARM; ++i) {
+                const int src = SM.tau_src[lane][i];
+                const int sx = src / NSP < NM ? src / NSP : NM - 1;
+                const Real term = lds[SL::BS + src] * lds[SL::X + sx];   /* the zero slot: B = 0 */
+                sum += term; asum += fabs(term);
+            }
+            lds[SL::RHO + lane] = lam * (tc - sum);
+            lds[SL::RER + lane] = lam * (fabs(tc) + asum);
+        }
+        wave_sync();
+        Real wv[MPL], wtol[MPL];
+        sfor<0, MPL>([&](auto jI) {
+            constexpr int j = decltype(jI)::value;
+            Real w = 0, e = 0;
+#pragma unroll
+            for (int k = 0; k < NSP; ++k) {
+                const int dk = down[j][k] >= 0 ? down[j][k] : 0;
+                w += bown[j][k] * lds[SL::RHO + dk];
+                e += fabs(bown[j][k]) * lds[SL::RER + dk];
+            }
+            wv[j] = w - xv[j];
+            wtol[j] = tiny * (e + fabs(xv[j]));
+        });
+        if (mode == 0) {
+            /* CHECK: free the bound variable whose w points furthest inward */
+            Real best = 0;
+            Real sc[MPL];
+            int bad = 0;
+            sfor<0, MPL>([&](auto jI) {
+                constexpr int j = decltype(jI)::value;
+                bad |= (mi[j] < NM && !(wv[j] == wv[j])) ? 1 : 0;   /* a NaN came in */
+                Real v = fl[j] < Real(0) ? wv[j] : (fl[j] > Real(0) ? -wv[j] : Real(0));
+                v = (mi[j] < NM && !blk[j] && v > wtol[j]) ? v : Real(0);
+                sc[j] = v;
+                best = v > best ? v : best;
+            });
+            best = group_max<G>(best);
+            if (group_min<G>(-bad) < 0) {
+                done = true;
+                status = -2;
+            } else if (!(best > Real(0))) {
+                done = true;
+                status = it;
+            } else {
+                int cand = NM;
+                sfor<0, MPL>([&](auto jI) {
+                    constexpr int j = decltype(jI)::value;
+                    cand = (sc[j] == best && mi[j] < cand) ? mi[j] : cand;
+                });
+                const int t = group_min<G>(cand);
+                sfor<0, MPL>([&](auto jI) {
+                    constexpr int j = decltype(jI)::value;
+                    if (mi[j] == t) { fl[j] = Real(0); lds[SL::F + lane + j * G] = Real(0); }
+                });
+                tnew = t;
+                mode = 1;
+            }
+        }
+        if (!done && ++it > SL::CAP) {
+            done = true;
+            status = -1;
+        }
+        if (!done) {
+            wave_sync();
+            /* the masked matrix (bound rows and columns: identity) and, as row NM, the right-hand side */
+            for (int i = 0; i < NM; ++i) {
+                const bool fi = lds[SL::F + i] == Real(0);
+                sfor<0, MPL>([&](auto jI) {
+                    constexpr int j = decltype(jI)::value;
+                    const int t = lane + j * G;
+                    if (t <= i) {
+                        const int e = i * (i + 1) / 2 + t;
+                        const Real hv = lds[SL::H + e];
+                        lds[SL::A + e] = (fi && fl[j] == Real(0)) ? hv : (t == i ? Real(1) : Real(0));
+                    }
+                });
+            }
+            sfor<0, MPL>([&](auto jI) {
+                constexpr int j = decltype(jI)::value;
+                const int t = lane + j * G;
+                if (t < NM) lds[SL::A + NH + t] = fl[j] == Real(0) ? wv[j] : Real(0);
+            });
+            wave_sync();
+            /* Cholesky, right-looking; row NM comes out as L^-1 rhs */
+            bool ok = true;
+            for (int k = 0; k < NM && ok; ++k) {
+                const Real piv = lds[SL::A + k * (k + 1) / 2 + k];
+                ok = piv > Real(0);
+                if (ok) {
+                    const Real rp = Real(1) / sqrt(piv);
+                    for (int i = k + 1 + lane; i <= NM; i += G) lds[SL::A + i * (i + 1) / 2 + k] *= rp;
+                    if (lane == 0) lds[SL::D + k] = rp;
+                    wave_sync();
+                    for (int i = k + 1 + lane; i <= NM; i += G) {
+                        Real *ri = lds + SL::A + i * (i + 1) / 2;
+                        const Real lik = ri[k];
+                        const int je = i < NM ? i : NM - 1;
+                        for (int jc = k + 1; jc <= je; ++jc) ri[jc] -= lik * lds[SL::A + jc * (jc + 1) / 2 + k];
+                    }
+                    wave_sync();
+                }
+            }
+            if (!ok) {
+                done = true;
+                status = -2;
+            } else {
+                /* L^T dz = y, last row first */
+                for (int k = NM - 1; k >= 0; --k) {
+                    const Real zk = lds[SL::A + NH + k] * lds[SL::D + k];
+                    const Real *rk = lds + SL::A + k * (k + 1) / 2;
+                    for (int i = lane; i < k; i += G) lds[SL::A + NH + i] -= rk[i] * zk;
+                    if (lane == 0) lds[SL::Z + k] = zk;
+                    wave_sync();
+                }
+                /* the step: whole if it stays in the box, else to the first bound met */
+                Real zv[MPL], al[MPL], bd[MPL];
+                Real amin = Real(2);
+                sfor<0, MPL>([&](auto jI) {
+                    constexpr int j = decltype(jI)::value;
+                    const int t = lane + j * G;
+                    const bool fr = t < NM && fl[j] == Real(0);
+                    zv[j] = fr ? xv[j] + lds[SL::Z + (t < NM ? t : 0)] : xv[j];
+                    const bool under = fr && zv[j] < lo, over = fr && zv[j] > hi;
+                    bd[j] = under ? lo : hi;
+                    const Real den = zv[j] - xv[j];
+                    Real av = (under || over) ? (bd[j] - xv[j]) / den : Real(2);
+                    av = av < Real(0) ? Real(0) : av;     /* an under / over step has den != 0; rounding only */
+                    al[j] = (under || over) ? (av < Real(1) ? av : Real(1)) : Real(2);
+                    amin = al[j] < amin ? al[j] : amin;
+                });
+                amin = group_min<G>(amin);
+                if (amin > Real(1)) {   /* inside the box: take it, check again */
+                    sfor<0, MPL>([&](auto jI) {
+                        constexpr int j = decltype(jI)::value;
+                        xv[j] = zv[j];
+                        blk[j] = false;
+                    });
+                    mode = 0;
+                } else {
+                    int cand = NM;
+                    sfor<0, MPL>([&](auto jI) {
+                        constexpr int j = decltype(jI)::value;
+                        cand = (al[j] == amin && mi[j] < cand) ? mi[j] : cand;
+                    });
+                    const int jm = group_min<G>(cand);
+                    const bool back = jm == tnew && amin == Real(0);   /* freed by rounding noise */
+                    sfor<0, MPL>([&](auto jI) {
+                        constexpr int j = decltype(jI)::value;
+                        const int t = lane + j * G;
+                        if (t < NM && fl[j] == Real(0)) xv[j] = xv[j] + amin * (zv[j] - xv[j]);
+                        if (mi[j] == jm) {
+                            xv[j] = bd[j];
+                            fl[j] = bd[j] == lo ? Real(-1) : Real(1);
+                            blk[j] = back;
+                            lds[SL::F + t] = fl[j];
+                        }
+                        /* a free variable the partial step leaves outside by rounding stays inside */
+                        xv[j] = xv[j] < lo ? lo : (xv[j] > hi ? hi : xv[j]);
+                    });
+                    if (back) mode = 0;
+                }
+                tnew = -1;
+                sfor<0, MPL>([&](auto jI) {
+                    constexpr int j = decltype(jI)::value;
+                    const int t = lane + j * G;
+                    if (t < NM) lds[SL::X + t] = xv[j];
+                });
+            }
+        }
+        wave_sync();
+    }
+    /* outputs: act by muscle; tau_muscle = B a + c, residual = tau - tau_muscle by dof */
+    sfor<0, MPL>([&](auto jI) {
+        constexpr int j = decltype(jI)::value;
+        if (mi[j] < NM) GAT(a.act, (size_t)idx * NM + mi[j], (size_t)a.n * NM) = xv[j];
+    });
+    if (lane == 0 && a.status) a.status[idx] = status;
+    if (lane < ND && (a.residual || a.tau_muscle)) {
+        Real sum = 0;
+#pragma unroll
+        for (int i = 0; i < T::MAXARM; ++i) {
+            const int src = SM.tau_src[lane][i];
+            const int sx = src / NSP < NM ? src / NSP : NM - 1;
+            sum += lds[SL::BS + src] * lds[SL::X + sx];
+        }
+        const Real tm = sum + cq;
+        if (a.tau_muscle) GAT(a.tau_muscle, (size_t)idx * ND + lane, (size_t)a.n * ND) = tm;
+        if (a.residual) GAT(a.residual, (size_t)idx * ND + lane, (size_t)a.n * ND) = tq - tm;
+    }
+}
+
 /* ---------------------------------------------------------------- kernel
  * Launch arguments of one env segment (one handle).  mode 0: env step
  * (optionally with in-kernel auto-reset); mode 1: reset the listed envs.
@@ -4502,6 +4976,15 @@ struct MuscleEvalCall {   /* bioim_muscle_eval's arguments (untyped), for Ops::m
     void *length, *speed, *dldq, *fiber, *tau;
 };
 
+struct StaticOptCall {   /* bioim_static_opt's arguments (untyped), for Ops::so_launch */
+    int n;
+    const void *q, *u, *tau, *row_weight;
+    double lo, hi;
+    int passive;
+    void *act, *residual, *tau_muscle, *capacity;
+    int32_t *status;
+};
+
 struct Ops {
     const char *topo;   /* the topology struct's name (fused-pair lookup) */
     int lanes;
@@ -4513,6 +4996,8 @@ struct Ops {
     void (*id_launch)(bioim_handle_t *, int op, int n, const void *q, const void *u, const void *v, void *out);
     /* bioim_muscle_eval's launcher; null for a torque topology (no muscles, no kernel) */
     void (*ma_launch)(bioim_handle_t *, const MuscleEvalCall &);
+    /* bioim_static_opt's launcher; null for a torque topology and for an fp32 handle (fp64 kernels only) */
+    void (*so_launch)(bioim_handle_t *, const StaticOptCall &);
     /* the fused rollout kernel's launcher; null where that instantiation is
      * left out (bioim_rollout then loops over `launch`) */
     void (*rollout)(bioim_handle_t *, const RolloutCall &);
@@ -4789,6 +5274,23 @@ template <class T, typename Real> void ma_launch_impl(bioim_handle_t *h, const M
     hipLaunchKernelGGL((ma_kernel<T, Real>), dim3((c.n + EPB - 1) / EPB), dim3(BIOIM_EPB * T::G), lds, h->stream, a);
 }
 
+template <class T> void so_launch_impl(bioim_handle_t *h, const StaticOptCall &c) {
+    constexpr int EPB = BIOIM_EPB;
+    using Real = double;
+    SoArgs<T, Real> a;
+    a.Mg = reinterpret_cast<const DModel<Real> *>(h->model);
+    a.Sg = reinterpret_cast<const SModel<T, Real> *>(h->smodel);
+    a.n = c.n; a.passive = c.passive;
+    a.q = reinterpret_cast<const Real *>(c.q); a.u = reinterpret_cast<const Real *>(c.u);
+    a.tau = reinterpret_cast<const Real *>(c.tau); a.row_weight = reinterpret_cast<const Real *>(c.row_weight);
+    a.lo = c.lo; a.hi = c.hi;
+    a.act = reinterpret_cast<Real *>(c.act); a.residual = reinterpret_cast<Real *>(c.residual);
+    a.tau_muscle = reinterpret_cast<Real *>(c.tau_muscle); a.capacity = reinterpret_cast<Real *>(c.capacity);
+    a.status = c.status;
+    constexpr size_t lds = lds_bytes<T, Real, false>();
+    hipLaunchKernelGGL((so_kernel<T, Real>), dim3((c.n + EPB - 1) / EPB), dim3(BIOIM_EPB * T::G), lds, h->stream, a);
+}
+
 template <class T, typename Real> int upload_smodel(bioim_handle_t *h) {
     static_assert(lds_bytes<T, Real, true>() <= 163840, "LDS image + env regions exceed 160 KiB");
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&env_kernel<T, Real, false, false>),
@@ -4814,6 +5316,9 @@ template <class T, typename Real> int upload_smodel(bioim_handle_t *h) {
     if constexpr (T::NM > 0)
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&ma_kernel<T, Real>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, Real, false>()));
+    if constexpr (T::NM > 0 && std::is_same<Real, double>::value)
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&so_kernel<T, double>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, double, false>()));
     constexpr size_t B = smodel_bytes<T, Real>();
     std::vector<unsigned char> img(B, 0);
     build_smodel<T, Real>(h->pack, *reinterpret_cast<SModel<T, Real> *>(img.data()));
@@ -4830,9 +5335,11 @@ template <class T> bool pick(const bioim_modelpack_t &p, int precision, Ops &ops
     ops.lanes = T::G;
     ops.cache_dim = CacheLay<T>::DIM;
     ops.ma_launch = nullptr;
+    ops.so_launch = nullptr;
     if constexpr (T::NM > 0) {
         if (precision == 64) ops.ma_launch = &ma_launch_impl<T, double>;
         else ops.ma_launch = &ma_launch_impl<T, float>;
+        if (precision == 64) ops.so_launch = &so_launch_impl<T>;
     }
     if (precision == 64) {
         ops.launch = &launch_impl<T, double>;
@@ -5534,6 +6041,26 @@ int bioim_muscle_eval(bioim_handle_t *h, int n, const void *q, const void *u, co
     HIPCHK(hipSetDevice(h->device));
     const MuscleEvalCall c{n, q, u, act, lce, length, speed, dldq, fiber, tau};
     h->ops.ma_launch(h, c);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int bioim_static_opt(bioim_handle_t *h, int n, const void *q, const void *u, const void *tau, const void *row_weight,
+                     double lo, double hi, int passive, void *act, void *residual, void *tau_muscle, void *capacity,
+                     int32_t *status) {
+    if (!h) return fail(BIOIM_E_ARG, "bioim_static_opt: null handle");
+    if (n < 0) return fail(BIOIM_E_ARG, "bioim_static_opt: negative n");
+    if (n > 0 && !q) return fail(BIOIM_E_ARG, "bioim_static_opt: null q");
+    if (!tau) return fail(BIOIM_E_ARG, "bioim_static_opt: null tau");
+    if (!act) return fail(BIOIM_E_ARG, "bioim_static_opt: null act");
+    if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi))
+        return fail(BIOIM_E_ARG, "bioim_static_opt: the bounds must be finite with lo < hi");
+    if (h->nmuscle <= 0) return fail(BIOIM_E_ARG, "bioim_static_opt: the model has no muscles");
+    if (h->precision != 64 || !h->ops.so_launch) return fail(BIOIM_E_ARG, "bioim_static_opt: fp64 handles only");
+    if (n == 0) return 0;
+    HIPCHK(hipSetDevice(h->device));
+    const StaticOptCall c{n, q, u, tau, row_weight, lo, hi, passive, act, residual, tau_muscle, capacity, status};
+    h->ops.so_launch(h, c);
     HIPCHK(hipGetLastError());
     return 0;
 }

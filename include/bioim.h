@@ -184,6 +184,62 @@ int bioim_id_eval(bioim_handle_t *h, int op, int n, const void *q, const void *u
 #define BIOIM_MUSCLE_FIBER_DIM 5
 int bioim_muscle_eval(bioim_handle_t *h, int n, const void *q, const void *u, const void *act, const void *lce,
                       void *length, void *speed, void *dldq, void *fiber, void *tau);
+/* Static optimization (OpenSim's StaticOptimization, the step that joins
+ * InverseDynamics and MuscleAnalysis) on the handle's model, batched over n
+ * arbitrary states — not the handle's envs: the env state and the realize
+ * cache are neither read nor written.  Per state: the activations a that
+ * produce the target generalized force tau (normally bioim_id_eval's
+ * BIOIM_ID_RESIDUAL at (q, u, q'')) at least effort,
+ *     minimize sum_m a_m^2 + sum_d lam_d (tau_d - (B a + c)_d)^2
+ *     subject to lo <= a_m <= hi,
+ * with OpenSim's assumptions (use_muscle_physiology, rigid tendons), which
+ * make the muscle force linear in the activation.  With L, dL/dt, dL/dq as
+ * bioim_muscle_eval's length, speed, dldq, per muscle
+ *     w = l_opt sin(alpha_opt),  l_t = max(L - l_ts, 0),
+ *     l_m = max(sqrt(l_t^2 + w^2), l_min),  cos = sqrt(l_m^2 - w^2) / l_m,
+ *     Fa = F0 fal(l_m / l_opt) fv(dL/dt cos / (l_opt v_max)) cos   (the active
+ *          capacity: the force at a = 1),
+ *     Fp = F0 fpe(l_m / l_opt) cos                               (the passive force),
+ * both cut at 0 from below (a muscle without capacity has B = 0 exactly and
+ * stays at lo), and dL/dq taken as the exact 0 it is on a dof that moves
+ * every point of the path (a rigid motion of the path; a moving point's own
+ * coordinate excepted), so a muscle without a moment arm stays at lo too,
+ * the curves the step's own; B[d][m] = -dL_m/dq_d Fa_m, and c_d = -sum_m
+ * dL_m/dq_d Fp_m when `passive` is nonzero, else 0 (OpenSim's balance carries
+ * the active force only).  The exponent is 2 only.  The residual tau - B a - c
+ * is OpenSim's reserve actuators: a reserve of optimal torque w_d is
+ * lam_d = 1 / w_d^2; lam_d = 0 leaves row d out.  Rows no muscle spans (the
+ * floating base) do not influence a.  H = I + B^T lam B >= I: the minimizer
+ * is unique.
+ *   q, u, tau  [n][ndof]   device, dof order as for bioim_id_eval (u NULL: 0);
+ *   row_weight [ndof]      device, lam_d >= 0 (the caller's contract); NULL: all 1;
+ *   act        [n][nmuscle]     the activations (required);
+ *   tau_muscle [n][ndof]        B a + c;
+ *   residual   [n][ndof]        tau - tau_muscle, on every dof;
+ *   capacity   [n][nmuscle][2]  Fa, Fp;
+ *   status     [n] int32        the solver's passes (>= 0), -1: the iteration
+ *     cap was hit, -2: a factorization failed (a pivot <= 0, which H >= I
+ *     excludes, or a NaN that came in); act then holds the last feasible
+ *     iterate, not the minimizer.
+ * Outputs other than act may be NULL.  The solve is exact and finite: a
+ * primal active-set (BVLS) iteration from a = lo with a Cholesky
+ * factorization per pass, ties to the lowest muscle index; no stop tolerance
+ * (cond(H) reaches 3e5 at unit reserves).  The cap is 8 nmuscle passes (112 /
+ * 176 / 152 for 14 / 22 / 19 muscles); the most observed is 21 / 29 / 18 (over
+ * 4096 / 4096 / 64 states at unit reserves).  A state's result does not depend on n or on the other
+ * states, and a repeated call repeats it bit for bit.
+ * fp64 handles only: the normal equations behind H leave single precision
+ * no digits at cond(H) ~ 1e5-1e6.  BIOIM_E_ARG, before any device call and in
+ * this order, for: a null handle, n < 0, null q with n > 0, null tau, null
+ * act, bounds that are not finite with lo < hi, a model without muscles, an
+ * fp32 handle.  n == 0 returns BIOIM_OK without a launch.  Asynchronous on
+ * the handle's stream; synchronizes nothing.  No reference counterpart (the
+ * reference ships StaticOptimization results, not the solver). */
+int bioim_static_opt(bioim_handle_t *h, int n, const void *q, const void *u, const void *tau,
+                     const void *row_weight /* device [ndof], NULL = all 1 */, double lo, double hi, int passive,
+                     void *act /* [n][nmuscle], required */, void *residual /* [n][ndof] */,
+                     void *tau_muscle /* [n][ndof] */, void *capacity /* [n][nmuscle][2]: Fa, Fp */,
+                     int32_t *status /* [n]: iterations used, or -1 cap hit, -2 factorization failed */);
 /* OsimModel calls on single envs (the reference's physics facade,
  * opensim_wrapper.py:92-332), for callers that drive the model directly
  * (tests/example_position_control.py:203-223; the env methods
