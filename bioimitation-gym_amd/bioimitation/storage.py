@@ -43,6 +43,53 @@ def write_sto(path: str, labels: List[str], data: np.ndarray, name: str = 'Stora
             fh.write('\t'.join(f'{v:.10f}' for v in row) + '\n')
 
 
+TRC_UNITS = {'mm': 1e-3, 'cm': 1e-2, 'm': 1.0}
+
+
+def read_trc(path: str):
+    """A marker trajectory file (``.trc``, tab-separated) as (time [n], marker
+    names, X [n][nmarkers][3] in metres).  The second line names the header
+    fields and the third holds their values (``Units``: mm, cm or m); the
+    fourth is ``Frame#  Time  <name> <blank> <blank> ...``, the fifth the
+    ``X1 Y1 Z1`` labels; data rows follow (blank lines skipped).  A blank or
+    non-numeric field (a gap) becomes NaN; a row may stop short of its last
+    markers, which are then gaps too."""
+    with open(path, 'r') as fh:
+        lines = fh.read().splitlines()
+    if len(lines) < 5:
+        raise ValueError(f'{path}: not a .trc file (fewer than 5 lines)')
+    keys, vals = lines[1].split('\t'), lines[2].split('\t')
+    if len(keys) < 2:      # space-separated header fields
+        keys, vals = lines[1].split(), lines[2].split()
+    header = {k.strip(): v.strip() for k, v in zip(keys, vals) if k.strip()}
+    unit = header.get('Units', 'm').lower()
+    if unit not in TRC_UNITS:
+        raise ValueError(f'{path}: unknown Units {unit!r} (expected one of {sorted(TRC_UNITS)})')
+    names = [t.strip() for t in lines[3].split('\t')[2:] if t.strip()]
+    if not names:
+        names = lines[3].split()[2:]
+    nm = len(names)
+    time, rows = [], []
+
+    def num(t):
+        try:
+            return float(t)
+        except ValueError:
+            return math.nan
+    for ln in lines[5:]:
+        if not ln.strip():
+            continue
+        f = ln.split('\t')
+        if len(f) < 2:      # space-separated rows cannot hold blank fields
+            f = ln.split()
+        v = [num(t) for t in f[2:2 + 3 * nm]]
+        v += [math.nan] * (3 * nm - len(v))
+        time.append(num(f[1]))
+        rows.append(v)
+    X = np.array(rows, dtype=np.float64).reshape(len(rows), nm, 3) * TRC_UNITS[unit]
+    return np.array(time, dtype=np.float64), names, X
+
+
 def resample_linear(time: np.ndarray, data: np.ndarray, dt: float):
     """Storage::resampleLinear: uniform rows t0 + dt*i up to the last time."""
     t0, tf = float(time[0]), float(time[-1])

@@ -3127,6 +3127,360 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_e
     }
 }
 
+/* ------------------------------------------------------ inverse kinematics
+ * bioim_ik_solve (include/bioim.h): per frame the coordinates that bring the
+ * model's markers closest to the measured ones,
+ *     min sum_i w_i |x_i(q) - xe_i|^2 + sum_d c_d (q_d - qt_d)^2,
+ * x_i = o_b + R_b loc_i on the marker's composite body.  fp64 only.
+ *
+ * ma_kernel's launch shape (one frame per G lanes, the model image in LDS).
+ * One loop body serves every evaluation: the kinematics prologue at a trial q
+ * (frames KB and ground-frame Plucker columns S), then the marker pass: lane
+ * l takes the markers l, l + G, ... (tables and measurements from global
+ * memory), forms x_i, the residual r_i and the rows J_id = Omega_d x x_i + V_d
+ * (exact 0 where dof d is not on the body's root chain, SM.dofmask) and adds
+ * w_i J_id . J_ie, w_i J_id . r_i and w_i |r_i|^2 to its own partial sums in
+ * registers; a fixed xor butterfly over the G lanes then leaves the entries
+ * of the packed lower A = J^T W J + C, of g = J^T W r + C (q - qt) and f in
+ * every lane, so no nm x ndof Jacobian and no per-marker array is stored (nm
+ * is bounded by BIOIM_IK_MAX_MARKERS only).  The sums of all entries at once
+ * do not fit the registers of the 14-dof models: the rows of A are taken in
+ * IkLay::NBLK blocks, one marker pass each.  With float_origin the frames sit
+ * in a ground frame shifted by x0 = pelvis_tx, which moves with every trial
+ * q: the measured point is shifted with it, and the columns are the
+ * world-frame derivatives at the shifted point.
+ *
+ * Solver (the rule of include/bioim.h): damped Gauss-Newton.  mu starts at
+ * 1e-3 max diag A.  Each iteration solves (A + mu I) dq = -g by so_kernel's
+ * Cholesky factorization in LDS (g as row ND), evaluates at q + dq, and
+ * accepts if f_new <= f (1 + 64 eps) or max |dq| <= tol: then either returns
+ * (max |dq| <= tol) or takes the A and g of the new point and mu / 4; a
+ * rejected step keeps A and g and retries with 8 mu.  A and g of the last
+ * accepted point live in the frame's MP / RHS slots (the dynamics' system
+ * matrix and right-hand side, which the kinematics prologue never writes);
+ * the union region behind Lay::U is overwritten by every prologue and holds
+ * only the factorization's work area (IkLay), between one evaluation and the
+ * next prologue; q, f, mu, the step and the iteration count stay in
+ * registers.  When the solve ends, one more prologue and marker pass at the
+ * returned q writes the outputs.
+ *
+ * The 4 frames of a wave need different iteration counts: every lane loops
+ * under its own frame's state (uniform over the frame's G lanes); only
+ * wave_sync orders the LDS traffic, and no workgroup barrier follows the
+ * idx >= n exit.  No atomics, sums in a fixed order: a frame's result does
+ * not depend on n or its neighbours. */
+template <class T, typename Real> struct IkArgs {
+    const DModel<Real> *Mg;
+    const SModel<T, Real> *Sg;
+    int n, nm, max_iter;
+    const int32_t *marker_body;
+    const Real *marker_loc, *weight, *x_exp, *q0, *coord_weight, *q_target;
+    Real tol;
+    Real *q, *markers, *err, *jacobian;
+    int32_t *status;
+};
+
+/* the blocks of rows of A the marker passes take one at a time (the partial
+ * sums of all NP + ND entries at once do not fit the registers of the 14-dof
+ * models), and the solver's map of the union region: free from the last
+ * kin_column to the next prologue, which is when the factorization runs */
+template <class T, typename Real> struct IkLay {
+    using LY = Lay<T, Real>;
+    static constexpr int ND = LY::ND, NP = LY::NP;
+    static constexpr int row0(int c) {
+        return c <= 0 ? 0 : (c == 1 ? ND / 2 : (c == 2 ? (ND * 7 + 5) / 10 : (c == 3 ? (ND * 13 + 7) / 15 : ND)));
+    }
+    static constexpr int NBLK = 4;
+    static constexpr int W = LY::U;            /* [NP + ND] A + mu I, then its factor; row ND: g, then L^-1 g */
+    static constexpr int D = W + NP + ND;      /* [ND] reciprocal pivots */
+    static constexpr int Z = D + ND;           /* [ND] z = -dq           */
+    static constexpr int END = Z + ND;
+    static_assert(row0(1) > 0 && row0(1) <= row0(2) && row0(2) <= row0(3) && row0(3) <= ND, "row blocks in order");
+    static_assert(END <= LY::SIZE0, "the solver's data must fit in the union region");
+};
+
+template <class T, typename Real>
+__global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_eu(1, 1))) void ik_kernel(IkArgs<T, Real> a) {
+    using LY = Lay<T, Real>;
+    using PL = Planar<T>;
+    using IK = IkLay<T, Real>;
+    constexpr int G = T::G, ND = LY::ND, NB = T::NB, NP = LY::NP, EPB = BIOIM_EPB;
+    constexpr size_t SMB = smodel_bytes<T, Real>();
+    static_assert(LY::RHS == LY::MP + NP, "g is row ND of the packed matrix");
+    constexpr bool BFK = T::PLANAR || BIOIM_BF_SPATIAL, BF3 = !T::PLANAR;
+    constexpr bool BFK_FN = BFK || (BF3 && (BIOIM_BF3 & 1));
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    {
+        const uint4 *src = reinterpret_cast<const uint4 *>(a.Sg);
+        uint4 *dst = reinterpret_cast<uint4 *>(smem_raw);
+        for (int i = threadIdx.x; i < (int)(SMB / 16); i += BIOIM_EPB * G) dst[i] = src[i];
+    }
+    __syncthreads();
+    const SModel<T, Real> &SM = *reinterpret_cast<const SModel<T, Real> *>(smem_raw);
+    const DModel<Real> &M = *a.Mg;
+    const int lane = threadIdx.x % G, slot = threadIdx.x / G;
+    const int idx = blockIdx.x * EPB + slot;
+    if (idx >= a.n) return;
+    Real *lds = reinterpret_cast<Real *>(smem_raw + SMB) + slot * LY::SIZE;
+    const int nm = a.nm, max_iter = a.max_iter;
+    const Real tol = a.tol;
+    const size_t rows = (size_t)a.n * nm;
+    /* dof lanes: the accepted iterate, the trial point, the coordinate task */
+    Real qa = 0, qt = 0, cw = 0, qg = 0;
+    if (lane < ND) {
+        qa = GAT(a.q0, (size_t)idx * ND + lane, (size_t)a.n * ND);
+        if (a.coord_weight) {
+            cw = a.coord_weight[lane];
+            qg = GAT(a.q_target, (size_t)idx * ND + lane, (size_t)a.n * ND);
+        }
+    }
+    qt = qa;
+    Real f = 0, mu = 0, step = 0;
+    int it = 0, status = 0;
+    bool first = true, fin = max_iter == 0;
+    /* marker i at the frames in LDS: its point x (shifted ground frame), the
+     * residual r and weight ww (0, 0: left out), the dofs on its root chain */
+    auto marker_eval = [&](int i, Real x0, Real (&x)[3], Real (&r)[3], Real &ww, unsigned &dm) {
+        const int b = a.marker_body[i];
+        const Real w = a.weight[i];
+        Real loc[3], xe[3], K[12];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            loc[k] = a.marker_loc[3 * i + k];
+            xe[k] = GAT(a.x_exp, ((size_t)idx * nm + i) * 3 + k, rows * 3);
+        }
+        const Real *kb = lds + LY::KB + 18 * b;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) K[k] = kb[k];
+        PL::rot(K);
+        mv3(K, loc, x);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) x[k] += K[9 + k];
+        /* a gap in the measurement (NaN) or no weight: the marker is left out */
+        const bool used = xe[0] == xe[0] && xe[1] == xe[1] && xe[2] == xe[2] && w > Real(0);
+        ww = used ? w : Real(0);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) r[k] = used ? x[k] - xe[k] + (k == 0 ? x0 : Real(0)) : Real(0);
+        dm = SM.dofmask[b];
+    };
+    /* row d of the marker's Jacobian from dof d's column */
+    auto jac_row = [&](auto dI, const Real (&x)[3], unsigned dm, Real (&Jd)[3]) {
+        constexpr int d = decltype(dI)::value;
+        Real sc[6], t[3];
+        /* spatial models: an opaque offset, so the columns are read again per
+         * marker instead of hoisted out of the marker loop into 6 ND registers
+         * (the 14-dof kernels otherwise spill) */
+        int so = LY::S + 6 * d;
+        if constexpr (!T::PLANAR) asm volatile("" : "+v"(so));
+#pragma unroll
+        for (int k = 0; k < 6; ++k) sc[k] = lds[so + k];
+        PL::col(sc);
+        cross3(sc, x, t);
+        const bool on = (dm >> d) & 1u;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) Jd[k] = on ? t[k] + sc[3 + k] : Real(0);
+    };
+    while (true) {
+        /* the kinematics prologue at the trial point */
+        publish_coords<T, Real>(M, SM, lds, lane, qt, Real(0));
+        if (lane < ND) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) lds[LY::SL + 6 * lane + i] = 0;
+        }
+        wave_sync();
+        Real x0 = 0;
+        if constexpr (T::TX >= 0) {
+            if constexpr (T::coord_dof[T::TX] >= 0) x0 = M.float_origin ? lds[LY::QF + T::TX] : Real(0);
+        }
+        fn_slots<BFK_FN, T, Real>(SM, lds, lane);
+        if (lane < NB) kin_local<T, Real>(SM, lds, lane);
+        if (lane == NB) kin_ground<T, Real>(lds, x0);
+        wave_sync();
+        if (lane < NB) kin_chain<T, Real>(SM, lds, lane, x0);
+        wave_sync();
+        if (lane < ND) kin_column<T, Real>(SM, lds, lane);
+        wave_sync();   /* frames and columns are out; the union region (LOC / SL) is free until the next prologue */
+        if (fin) {
+            /* the outputs at the returned q */
+            Real fm = 0, sw = 0, dmax = 0;
+            for (int i = lane; i < nm; i += G) {
+                Real x[3], r[3], ww;
+                unsigned dm;
+                marker_eval(i, x0, x, r, ww, dm);
+                const Real rr = dot3(r, r);
+                fm += ww * rr;
+                sw += ww;
+                dmax = rr > dmax ? rr : dmax;
+                if (a.markers) {
+                    Real *mo = a.markers + GIDX(((size_t)idx * nm + i) * 3, rows * 3);
+                    mo[0] = x[0] + x0; mo[1] = x[1]; mo[2] = x[2];
+                }
+                if (a.jacobian) {
+                    Real *jo = a.jacobian + GIDX(((size_t)idx * nm + i) * 3 * ND, rows * 3 * ND);
+                    sfor<0, ND>([&](auto dI) {
+                        constexpr int d = decltype(dI)::value;
+                        Real Jd[3];
+                        jac_row(dI, x, dm, Jd);
+                        jo[d] = Jd[0]; jo[ND + d] = Jd[1]; jo[2 * ND + d] = Jd[2];
+                    });
+                }
+            }
+            fm = group_sum<G>(fm);
+            sw = group_sum<G>(sw);
+            dmax = group_max<G>(dmax);
+            if (a.err && lane == 0) {
+                Real *eo = a.err + GIDX((size_t)idx * 2, (size_t)a.n * 2);
+                eo[0] = sw > Real(0) ? sqrt(fm / sw) : Real(0);
+                eo[1] = sqrt(dmax);
+            }
+            break;
+        }
+        /* the marker passes, one per block of rows of A (IkLay::row0): the
+         * lane's partial sums of the block's entries and of its g entries, the
+         * butterfly, then the entries to MP / RHS.  The first block also sums f
+         * and decides on the step, so a rejected step stops after it and leaves
+         * A and g of the accepted point where they are */
+        const Real dqt = qt - qg;
+        bool accept = false, conv = false;
+        sfor<0, IK::NBLK>([&](auto cI) {
+            constexpr int c = decltype(cI)::value;
+            constexpr int r0 = IK::row0(c), r1 = IK::row0(c + 1);
+            constexpr int e0 = r0 * (r0 + 1) / 2, NE = r1 * (r1 + 1) / 2 - e0, NR = r1 - r0;
+            if (c > 0 && !(accept && !conv)) return;
+            Real acc[NE + NR];
+            sfor<0, NE + NR>([&](auto kI) { acc[decltype(kI)::value] = 0; });
+            Real fm = 0;
+            for (int i = lane; i < nm; i += G) {
+                Real x[3], r[3], ww, J[r1][3];
+                unsigned dm;
+                marker_eval(i, x0, x, r, ww, dm);
+                if constexpr (c == 0) fm += ww * dot3(r, r);
+                sfor<0, r1>([&](auto dI) { jac_row(dI, x, dm, J[decltype(dI)::value]); });
+                sfor<r0, r1>([&](auto dI) {
+                    constexpr int d = decltype(dI)::value;
+                    const Real wj[3] = {ww * J[d][0], ww * J[d][1], ww * J[d][2]};
+                    sfor<0, d + 1>([&](auto eI) {
+                        constexpr int e = decltype(eI)::value;
+                        acc[d * (d + 1) / 2 + e - e0] += dot3(wj, J[e]);
+                    });
+                    acc[NE + d - r0] += dot3(wj, r);
+                });
+            }
+            /* the coordinate tasks (dof lane d: its own diagonal entry) */
+            sfor<r0, r1>([&](auto dI) {
+                constexpr int d = decltype(dI)::value;
+                acc[d * (d + 1) / 2 + d - e0] += lane == d ? cw : Real(0);
+                acc[NE + d - r0] += lane == d ? cw * dqt : Real(0);
+            });
+            sfor<0, NE + NR>([&](auto kI) {
+                constexpr int k = decltype(kI)::value;
+                acc[k] = group_sum<G>(acc[k]);
+                if constexpr (k % 8 == 7) __builtin_amdgcn_sched_barrier(0);   /* a few butterflies in flight, not all */
+            });
+            if constexpr (c == 0) {
+                const Real fn = group_sum<G>(fm) + group_sum<G>(cw * dqt * dqt);
+                if (first) {
+                    accept = true;
+                    if (!(fn == fn)) {   /* a NaN that came in */
+                        status = -2;
+                        fin = true;
+                    }
+                } else {
+                    conv = step <= tol;
+                    accept = fn <= f * (Real(1) + Real(64) * Real(2.220446049250313e-16)) || conv;
+                }
+                if (accept) {
+                    qa = qt;
+                    f = fn;
+                    if (conv) {
+                        status = it;
+                        fin = true;
+                    } else if (!first) {
+                        mu *= Real(0.25);
+                    }
+                } else {
+                    mu *= Real(8);
+                }
+            }
+            if (accept && !conv) {
+                sfor<0, NE>([&](auto kI) {
+                    constexpr int k = decltype(kI)::value;
+                    if (lane == k % G) lds[LY::MP + e0 + k] = acc[k];
+                });
+                sfor<0, NR>([&](auto kI) {
+                    constexpr int k = decltype(kI)::value;
+                    if (lane == (NE + k) % G) lds[LY::RHS + r0 + k] = acc[NE + k];
+                });
+            }
+        });
+        wave_sync();
+        if (first) {
+            const Real dg = lane < ND ? lds[LY::MP + lane * (lane + 1) / 2 + lane] : Real(0);
+            mu = Real(1e-3) * group_max<G>(dg);
+            first = false;
+        }
+        if (!fin) {
+            if (it >= max_iter) {
+                status = -1;
+                fin = true;
+            } else {
+                ++it;
+                /* (A + mu I) dq = -g: the work copy (lane i: row i; row ND is g), then
+                 * so_kernel's right-looking Cholesky on the frame's lanes; row ND
+                 * comes out as L^-1 g */
+                if (lane <= ND) {
+                    const int o = lane * (lane + 1) / 2;
+                    for (int j = 0; j <= (lane < ND ? lane : ND - 1); ++j)
+                        lds[IK::W + o + j] = lds[LY::MP + o + j] + ((j == lane) ? mu : Real(0));
+                }
+                wave_sync();
+                bool ok = true;
+                for (int k = 0; k < ND && ok; ++k) {
+                    const Real piv = lds[IK::W + k * (k + 1) / 2 + k];
+                    ok = piv > Real(0);
+                    if (ok) {
+                        const Real rp = Real(1) / sqrt(piv);
+                        for (int i = k + 1 + lane; i <= ND; i += G) lds[IK::W + i * (i + 1) / 2 + k] *= rp;
+                        if (lane == 0) lds[IK::D + k] = rp;
+                        wave_sync();
+                        for (int i = k + 1 + lane; i <= ND; i += G) {
+                            Real *ri = lds + IK::W + i * (i + 1) / 2;
+                            const Real lik = ri[k];
+                            const int je = i < ND ? i : ND - 1;
+                            for (int jc = k + 1; jc <= je; ++jc) ri[jc] -= lik * lds[IK::W + jc * (jc + 1) / 2 + k];
+                        }
+                        wave_sync();
+                    }
+                }
+                Real dqd = 0;
+                if (ok) {
+                    /* L^T z = y, last row first; dq = -z */
+                    for (int k = ND - 1; k >= 0; --k) {
+                        const Real zk = lds[IK::W + NP + k] * lds[IK::D + k];
+                        const Real *rk = lds + IK::W + k * (k + 1) / 2;
+                        for (int i = lane; i < k; i += G) lds[IK::W + NP + i] -= rk[i] * zk;
+                        if (lane == 0) lds[IK::Z + k] = zk;
+                        wave_sync();
+                    }
+                    dqd = lane < ND ? -lds[IK::Z + lane] : Real(0);
+                }
+                const bool bad = group_max<G>((dqd == dqd) ? Real(0) : Real(1)) > Real(0);
+                if (!ok || bad) {   /* a pivot <= 0, or a NaN that came in */
+                    status = -2;
+                    fin = true;
+                } else {
+                    step = group_max<G>(fabs(dqd));
+                    qt = qa + dqd;
+                }
+            }
+        }
+        if (fin) qt = qa;
+        wave_sync();
+    }
+    if (lane < ND) GAT(a.q, (size_t)idx * ND + lane, (size_t)a.n * ND) = qa;
+    if (lane == 0 && a.status) a.status[idx] = status;
+}
+
 /* ---------------------------------------------------------------- kernel
  * Launch arguments of one env segment (one handle).  mode 0: env step
  * (optionally with in-kernel auto-reset); mode 1: reset the listed envs.
@@ -4985,6 +5339,16 @@ struct StaticOptCall {   /* bioim_static_opt's arguments (untyped), for Ops::so_
     int32_t *status;
 };
 
+struct IkCall {   /* bioim_ik_solve's arguments (untyped), for Ops::ik_launch */
+    int n, nm;
+    const int32_t *marker_body;
+    const void *marker_loc, *weight, *x_exp, *q0, *coord_weight, *q_target;
+    double tol;
+    int max_iter;
+    void *q, *markers, *err, *jacobian;
+    int32_t *status;
+};
+
 struct Ops {
     const char *topo;   /* the topology struct's name (fused-pair lookup) */
     int lanes;
@@ -4998,6 +5362,8 @@ struct Ops {
     void (*ma_launch)(bioim_handle_t *, const MuscleEvalCall &);
     /* bioim_static_opt's launcher; null for a torque topology and for an fp32 handle (fp64 kernels only) */
     void (*so_launch)(bioim_handle_t *, const StaticOptCall &);
+    /* bioim_ik_solve's launcher (every topology); null for an fp32 handle (fp64 kernels only) */
+    void (*ik_launch)(bioim_handle_t *, const IkCall &);
     /* the fused rollout kernel's launcher; null where that instantiation is
      * left out (bioim_rollout then loops over `launch`) */
     void (*rollout)(bioim_handle_t *, const RolloutCall &);
@@ -5291,6 +5657,26 @@ template <class T> void so_launch_impl(bioim_handle_t *h, const StaticOptCall &c
     hipLaunchKernelGGL((so_kernel<T, Real>), dim3((c.n + EPB - 1) / EPB), dim3(BIOIM_EPB * T::G), lds, h->stream, a);
 }
 
+template <class T> void ik_launch_impl(bioim_handle_t *h, const IkCall &c) {
+    constexpr int EPB = BIOIM_EPB;
+    using Real = double;
+    IkArgs<T, Real> a;
+    a.Mg = reinterpret_cast<const DModel<Real> *>(h->model);
+    a.Sg = reinterpret_cast<const SModel<T, Real> *>(h->smodel);
+    a.n = c.n; a.nm = c.nm; a.max_iter = c.max_iter;
+    a.marker_body = c.marker_body;
+    a.marker_loc = reinterpret_cast<const Real *>(c.marker_loc); a.weight = reinterpret_cast<const Real *>(c.weight);
+    a.x_exp = reinterpret_cast<const Real *>(c.x_exp); a.q0 = reinterpret_cast<const Real *>(c.q0);
+    a.coord_weight = reinterpret_cast<const Real *>(c.coord_weight);
+    a.q_target = reinterpret_cast<const Real *>(c.q_target);
+    a.tol = c.tol;
+    a.q = reinterpret_cast<Real *>(c.q); a.markers = reinterpret_cast<Real *>(c.markers);
+    a.err = reinterpret_cast<Real *>(c.err); a.jacobian = reinterpret_cast<Real *>(c.jacobian);
+    a.status = c.status;
+    constexpr size_t lds = lds_bytes<T, Real, false>();
+    hipLaunchKernelGGL((ik_kernel<T, Real>), dim3((c.n + EPB - 1) / EPB), dim3(BIOIM_EPB * T::G), lds, h->stream, a);
+}
+
 template <class T, typename Real> int upload_smodel(bioim_handle_t *h) {
     static_assert(lds_bytes<T, Real, true>() <= 163840, "LDS image + env regions exceed 160 KiB");
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&env_kernel<T, Real, false, false>),
@@ -5319,6 +5705,9 @@ template <class T, typename Real> int upload_smodel(bioim_handle_t *h) {
     if constexpr (T::NM > 0 && std::is_same<Real, double>::value)
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&so_kernel<T, double>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, double, false>()));
+    if constexpr (std::is_same<Real, double>::value)
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&ik_kernel<T, double>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, double, false>()));
     constexpr size_t B = smodel_bytes<T, Real>();
     std::vector<unsigned char> img(B, 0);
     build_smodel<T, Real>(h->pack, *reinterpret_cast<SModel<T, Real> *>(img.data()));
@@ -5336,6 +5725,7 @@ template <class T> bool pick(const bioim_modelpack_t &p, int precision, Ops &ops
     ops.cache_dim = CacheLay<T>::DIM;
     ops.ma_launch = nullptr;
     ops.so_launch = nullptr;
+    ops.ik_launch = precision == 64 ? &ik_launch_impl<T> : nullptr;
     if constexpr (T::NM > 0) {
         if (precision == 64) ops.ma_launch = &ma_launch_impl<T, double>;
         else ops.ma_launch = &ma_launch_impl<T, float>;
@@ -6061,6 +6451,32 @@ int bioim_static_opt(bioim_handle_t *h, int n, const void *q, const void *u, con
     HIPCHK(hipSetDevice(h->device));
     const StaticOptCall c{n, q, u, tau, row_weight, lo, hi, passive, act, residual, tau_muscle, capacity, status};
     h->ops.so_launch(h, c);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int bioim_ik_solve(bioim_handle_t *h, int n, int nm, const int32_t *marker_body, const void *marker_loc,
+                   const void *weight, const void *x_exp, const void *q0, const void *coord_weight,
+                   const void *q_target, double tol, int max_iter, void *q, void *markers, void *err,
+                   void *jacobian, int32_t *status) {
+    if (!h) return fail(BIOIM_E_ARG, "bioim_ik_solve: null handle");
+    if (n < 0) return fail(BIOIM_E_ARG, "bioim_ik_solve: negative n");
+    if (nm < 1 || nm > BIOIM_IK_MAX_MARKERS)
+        return fail(BIOIM_E_ARG, "bioim_ik_solve: nm must be in [1, BIOIM_IK_MAX_MARKERS]");
+    if (n > 0 && (!marker_body || !marker_loc || !weight)) return fail(BIOIM_E_ARG, "bioim_ik_solve: null marker table");
+    if (n > 0 && !x_exp) return fail(BIOIM_E_ARG, "bioim_ik_solve: null x_exp");
+    if (n > 0 && !q0) return fail(BIOIM_E_ARG, "bioim_ik_solve: null q0");
+    if (n > 0 && !q) return fail(BIOIM_E_ARG, "bioim_ik_solve: null q");
+    if ((coord_weight == nullptr) != (q_target == nullptr))
+        return fail(BIOIM_E_ARG, "bioim_ik_solve: coord_weight and q_target go together");
+    if (!std::isfinite(tol) || tol < 0) return fail(BIOIM_E_ARG, "bioim_ik_solve: tol must be finite and >= 0");
+    if (max_iter < 0) return fail(BIOIM_E_ARG, "bioim_ik_solve: negative max_iter");
+    if (h->precision != 64 || !h->ops.ik_launch) return fail(BIOIM_E_ARG, "bioim_ik_solve: fp64 handles only");
+    if (n == 0) return 0;
+    HIPCHK(hipSetDevice(h->device));
+    const IkCall c{n, nm, marker_body, marker_loc, weight, x_exp, q0, coord_weight, q_target, tol, max_iter,
+                   q, markers, err, jacobian, status};
+    h->ops.ik_launch(h, c);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -240,6 +240,85 @@ int bioim_static_opt(bioim_handle_t *h, int n, const void *q, const void *u, con
                      void *act /* [n][nmuscle], required */, void *residual /* [n][ndof] */,
                      void *tau_muscle /* [n][ndof] */, void *capacity /* [n][nmuscle][2]: Fa, Fp */,
                      int32_t *status /* [n]: iterations used, or -1 cap hit, -2 factorization failed */);
+/* Marker inverse kinematics (OpenSim's InverseKinematicsTool, the first link
+ * of the chain IK -> InverseDynamics -> StaticOptimization) on the handle's
+ * model, batched over n frames — not the handle's envs: the env state and the
+ * realize cache are neither read nor written.  Per frame f, over the handle's
+ * dofs (locked coordinates are not dofs and keep their pack values, as in
+ * bioim_id_eval), it minimizes OpenSim's IK objective (IKMarkerTasks plus
+ * optional IKCoordinateTasks)
+ *     sum_i w_i |x_i(q) - x_exp[f][i]|^2 + sum_d c_d (q_d - q_target[f][d])^2,
+ * x_i(q) = o_b + R_b loc_i: marker i on its composite body b.
+ *   nm                     markers, 1 .. BIOIM_IK_MAX_MARKERS;
+ *   marker_body [nm] int32 composite-body index (a value outside the model is
+ *                          the caller's contract; the Python layer checks it);
+ *   marker_loc  [nm][3]    location in the composite body's frame;
+ *   weight      [nm]       w_i >= 0 (0 leaves the marker out); these three
+ *                          tables are shared by all frames of the call;
+ *   x_exp  [n][nm][3]      measured positions, ground frame, metres; a marker
+ *                          with a NaN component in a frame is left out of that
+ *                          frame (a gap in a .trc file; OpenSim skips it too);
+ *   q0     [n][ndof]       the start (required), dof order as for bioim_id_eval;
+ *   coord_weight [ndof], q_target [n][ndof]   c_d >= 0 and the coordinate
+ *                          tasks' values: both or neither (NULL: no tasks);
+ *   tol                    stop once an accepted step has max_d |dq_d| <= tol;
+ *   max_iter               >= 0; 0 evaluates only: the forward marker
+ *                          kinematics (markers, err, jacobian) at q0.
+ * Outputs (q required, the others may be NULL), all at the returned q:
+ *   q        [n][ndof];
+ *   markers  [n][nm][3]        the model's marker positions;
+ *   err      [n][2]            sqrt(sum w_i |r_i|^2 / sum w_i) and max |r_i|
+ *                              over the markers used (finite x_exp, w_i > 0):
+ *                              the weighted marker RMS and the largest marker
+ *                              distance, the figures of OpenSim's IK log; 0, 0
+ *                              when no marker is used;
+ *   jacobian [n][nm][3][ndof]  dx_i/dq_d (the station Jacobian), from the
+ *                              dofs' ground-frame Plucker columns: Omega_d x
+ *                              x_i + V_d; exact zeros where dof d is not on
+ *                              marker i's root chain;
+ *   status   [n] int32         >= 0: the iterations used; -1: max_iter was hit,
+ *                              q holds the last accepted iterate; -2: a pivot
+ *                              <= 0 or a NaN that came in (q0, a target), q
+ *                              holds the last accepted iterate (q0 if none).
+ *                              A frame with no marker used and no coordinate
+ *                              task has A = 0: it returns -2 and q = q0.
+ * The algorithm is fixed: damped Gauss-Newton on the normal equations
+ * A = J^T W J + C, g = J^T W r + C (q - q_target), f the objective.
+ *   1. mu = 1e-3 max_d A_dd at q0.
+ *   2. Every iteration solves (A + mu I) dq = -g by Cholesky (a pivot <= 0 ends
+ *      the frame with -2) and evaluates f at q + dq.
+ *   3. The step is accepted if f_new <= f (1 + 64 eps) or max |dq| <= tol.  An
+ *      accepted step with max |dq| <= tol returns; otherwise A and g are
+ *      re-formed at the new q and mu <- mu / 4.
+ *   4. A step that is not accepted leaves q, A and g, sets mu <- 8 mu and
+ *      solves again.
+ * Every solve counts as an iteration; before each, max_iter solves already
+ * done end the frame with -1.  (The "or small step" clause ends a frame at
+ * the rounding floor of f, where a decrease test alone rejects forever.)
+ * A frame's result does not depend on n or on the other frames, and a
+ * repeated call repeats it bit for bit.  BIOIM_IK_MAX_MARKERS is 64: the
+ * kernel keeps no per-marker storage (each lane sums its markers in
+ * registers), so the bound is not an LDS limit of any topology.
+ * Out of scope: coordinate range clamping (neither IK model the reference
+ * ships has a clamped coordinate; a solution may leave a coordinate's range).
+ * fp64 handles only: the iteration converges linearly on a trial with a
+ * large residual, and a step-size stop at 1e-9 rad has no meaning in single
+ * precision.  BIOIM_E_ARG, before any device call and in this order, for: a
+ * null handle, n < 0, nm < 1 or nm > BIOIM_IK_MAX_MARKERS, a null marker
+ * table (marker_body, marker_loc, weight) with n > 0, null x_exp with n > 0,
+ * null q0 with n > 0, null q with n > 0, exactly one of coord_weight /
+ * q_target, tol not finite or < 0, max_iter < 0, an fp32 handle.  n == 0
+ * returns BIOIM_OK without a launch.  Asynchronous on the handle's stream;
+ * synchronizes nothing.  No reference counterpart (the reference ships IK
+ * results, not the solver). */
+#define BIOIM_IK_MAX_MARKERS 64
+int bioim_ik_solve(bioim_handle_t *h, int n, int nm, const int32_t *marker_body /* [nm] */,
+                   const void *marker_loc /* [nm][3] */, const void *weight /* [nm] */,
+                   const void *x_exp /* [n][nm][3] */, const void *q0 /* [n][ndof], required */,
+                   const void *coord_weight /* [ndof] or NULL */, const void *q_target /* [n][ndof] or NULL */,
+                   double tol, int max_iter, void *q /* [n][ndof], required */, void *markers /* [n][nm][3] */,
+                   void *err /* [n][2] */, void *jacobian /* [n][nm][3][ndof] */,
+                   int32_t *status /* [n]: iterations used, or -1 cap hit, -2 factorization failed / NaN */);
 /* OsimModel calls on single envs (the reference's physics facade,
  * opensim_wrapper.py:92-332), for callers that drive the model directly
  * (tests/example_position_control.py:203-223; the env methods
