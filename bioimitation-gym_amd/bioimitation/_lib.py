@@ -21,7 +21,8 @@ EXPORTS = ['bioim_create', 'bioim_destroy', 'bioim_reset', 'bioim_step', 'bioim_
            'bioim_set_rk_budget', 'bioim_pending_count', 'bioim_set_active_mask', 'bioim_osim', 'bioim_osim_report_dim', 'bioim_eval_count', 'bioim_set_state_storage',
            'bioim_finished_count', 'bioim_set_rk_counters', 'bioim_copy_state', 'bioim_copy_state_rows', 'bioim_load_state',
            'bioim_clone_envs', 'bioim_debug_plane', 'bioim_rollout', 'bioim_rollout_fused', 'bioim_rollout_group',
-           'bioim_rollout_group_fused', 'bioim_muscle_eval', 'bioim_static_opt', 'bioim_ik_solve']
+           'bioim_rollout_group_fused', 'bioim_muscle_eval', 'bioim_static_opt', 'bioim_ik_solve',
+           'bioim_joint_reaction', 'bioim_realize_report']
 
 _lib = None
 
@@ -56,6 +57,7 @@ def load():
         'bioim_muscle_eval': (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         'bioim_static_opt': (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, vp, vp, vp, vp]),
         'bioim_ik_solve': (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_int, vp, vp, vp, vp, vp]),
+        'bioim_joint_reaction': (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
         'bioim_state_dim': (C.c_int, [vp]),
         'bioim_get_state': (C.c_int, [vp, dp]),
         'bioim_set_state': (C.c_int, [vp, dp]),
@@ -77,6 +79,7 @@ def load():
         'bioim_set_force_report': (C.c_int, [vp, vp]),
         'bioim_osim': (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, vp]),
         'bioim_osim_report_dim': (C.c_int, [vp]),
+        'bioim_realize_report': (C.c_int, [vp, vp, C.c_int, vp]),
         'bioim_eval_count': (C.c_int, [vp, C.POINTER(C.c_uint64)]),
         'bioim_finished_count': (C.c_int, [vp, C.POINTER(C.c_uint64)]),
         'bioim_set_rk_counters': (C.c_int, [vp, C.c_uint32, C.c_uint32]),

@@ -536,6 +536,83 @@ class VectorEnv:
         _, want, lam = so.check_args(pk.ndof, pk.nmuscle, q, u, qdd, tau, reserve, lo, hi, want)
         return so.solve_on(self, q, u, qdd, tau, lam, lo, hi, passive, want)
 
+    def _realize_report(self, ids, n):
+        """The REALIZE report rows of the n listed envs (``ids``: a checked
+        int32 device tensor) into ``self.osim_report``, on the env's stream.
+        ``bioim_realize_report`` does it without reading anything back; a
+        handle that has had an RK budget is refused there (its envs may be
+        suspended mid-step) and goes through ``osim('realize')``, which reads
+        the suspended-step flags back first."""
+        import torch
+        if getattr(self, 'osim_report', None) is None:
+            d = _lib.check(self._L.bioim_osim_report_dim(self._h))
+            self.osim_report = torch.zeros((self.num_envs, d), dtype=self.dtype, device=self.device)
+        if getattr(self, '_storage_grow', 0):
+            self._apply_storage_growth()
+        self._bind_stream()
+        if not getattr(self, '_realize_sync', False):
+            rc = self._L.bioim_realize_report(self._h, self._ptr(ids), n, self._ptr(self.osim_report))
+            if rc >= 0:
+                return self.osim_report
+            if b'RK budget' not in self._L.bioim_last_error():
+                _lib.check(rc)
+            self._realize_sync = True     # the refusal is for the handle's lifetime
+        return self.osim('realize', ids, want_obs=False)
+
+    def joint_reaction(self, env_ids=None, frame='child', on='child', want=('reaction',), rows=None):
+        """Joint reactions (``bioimitation.joint_reaction``) at the envs' own
+        state: {key: device tensor} for the keys of ``want``, one row per env
+        (or per listed env, in the list's order; distinct ids).  q and u are
+        gathered on the device (``state_rows``); the accelerations and the
+        muscles' tendon forces come from a REALIZE report of those envs
+        (``bioim_realize_report``), which leaves their next step bit for bit
+        what it is without it; then one ``bioim_joint_reaction`` launch with
+        the model's contact on.  All of it is enqueued on the env's stream: no
+        host round trip and no synchronization (ids given as a list or array
+        are checked on the host; a device tensor of ids is copied back once
+        for the check).  Two exceptions: an env that has had an RK budget
+        (``set_rk_budget``) realizes through ``osim``, which reads its
+        suspended-step flags back, and a precision=32 env's first call uploads
+        the fp64 model image.  ``rows``: state rows already gathered for these
+        envs.  The result labels itself for ``joint_reaction.write_sto``."""
+        import torch
+        from . import joint_reaction as jr
+        from .packdef import state_row_slices
+        pk = self.pack
+        jr.check_frame(frame, on)
+        if env_ids is None:
+            n, ids = self.num_envs, torch.arange(self.num_envs, dtype=torch.int32, device=self.device)
+        else:
+            host, ids = self._id_list(env_ids, 'env', distinct=True)
+            n = host.size
+        if rows is None:
+            rows = self.state_rows(env_ids=env_ids)
+        sl, _ = state_row_slices(pk.ndof, pk.nmuscle, pk.nact, pk.horizon)
+        q, u = (rows[:, sl[f]].to(self.dtype).contiguous() for f in ('q', 'u'))
+        _, want = jr.check_args(pk.ndof, pk.nmuscle, pk.ncbody, q, u, want=want, frame=frame, on=on)
+        if q.shape[0] != n:
+            raise ValueError(f'joint_reaction: rows has {q.shape[0]} rows for {n} envs')
+        qdd = ft = None
+        if n:
+            if ids is None:
+                ids = self._upload_ids(host)
+            rep = self._realize_report(ids, n).index_select(0, ids.long())
+            # report layout (include/bioim.h): time, istep, q[nc], u[nc], qdd[nc], 18 per OpenSim body, the COM's 9,
+            # then 7 per muscle, the tendon force last
+            if getattr(self, '_jr_dof_coord', None) is None:
+                coord_of = [c for d in range(pk.ndof) for c in range(pk.ncoord) if pk.coord[c].dof == d]
+                self._jr_dof_coord = torch.as_tensor(coord_of, dtype=torch.long).to(self.device, non_blocking=True)
+            k = 2 + 2 * pk.ncoord
+            qdd = rep[:, k:k + pk.ncoord].index_select(1, self._jr_dof_coord).contiguous()
+            if pk.nmuscle:
+                k = 2 + 3 * pk.ncoord + 18 * pk.nosbody + 9
+                ft = rep[:, k:k + 7 * pk.nmuscle].reshape(n, pk.nmuscle, 7)[:, :, 6].contiguous()
+        if getattr(self, '_jr_table', None) is None:
+            self._jr_table = jr.JointTable(self.env_id)
+        res = jr.Result(jr.launch(self, q, u, qdd, ft, None, True, frame, on, want))
+        res.table, res.frame, res.on = self._jr_table, frame, on
+        return res
+
     def load_state(self, rows, env_ids=None):
         """Write flat state rows (``state_rows``' layout: a contiguous
         (n, state_dim) float64 tensor on the env's device) into the listed

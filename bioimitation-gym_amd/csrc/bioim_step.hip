@@ -33,6 +33,7 @@
 
 #include <string>
 #include <type_traits>
+#include <memory>
 #include <vector>
 
 #include "bioim.h"
@@ -3481,6 +3482,342 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_e
     if (lane == 0 && a.status) a.status[idx] = status;
 }
 
+/* --------------------------------------------------------- joint reaction
+ * bioim_joint_reaction (include/bioim.h): per state the wrench every
+ * composite body's inboard joint carries.  ma_kernel's launch shape (one
+ * state per G lanes, the model image in LDS) and id_kernel's prologue up to
+ * body_inertia, which leaves the un-summed spatial inertias I_k (IC) and the
+ * velocity-product + gravity wrenches (WB) about the shifted origin.  Then
+ *   body lane k:   W_k = I_k (sum_{d on k's root path} S_d q''_d) + WB_k
+ *                        - contact (CW of k's spheres) - ext_k - muscles_k,
+ *   muscle lanes:  muscle_point_wrench sums each muscle's point forces per
+ *                  body in registers; the per-body sums over the lanes are the
+ *                  fixed butterfly of group_sum (6 NB sums), so every lane
+ *                  holds every body's muscle wrench and lane k picks its own
+ *                  (moments about o_k until then, shifted once),
+ *   body lane b:   F_b = sum_{k in subtree(b)} W_k (T::anc, fixed order),
+ *   outputs:       moment shifted to c_b, rotated into the requested frame;
+ *                  tau_joint_d = S_d . F_cb(d).
+ * Nothing is masked by Planar<T>: a planar model's out-of-plane components are
+ * loads its joints carry.  The q'' are staged in the RHS slots (no mass matrix
+ * is formed here); W_k and then F_b go to body k's own WB slot.  Every sum has
+ * a fixed order, so a state's result depends on nothing else.
+ * IO is the type of the caller's arrays (the handle's precision).  The model
+ * image and all arithmetic are fp64 on either handle: the Hunt-Crossley force
+ * turns 1e-7 m of a sphere's height into 0.1 N, and an fp32 kinematic chain
+ * places the sphere no better than that, ten times what rounding the inputs
+ * to fp32 costs.  An fp32 handle therefore gets a second, fp64 model image
+ * on its first call (jr_fp64_model) and converts only at the kernel's loads
+ * and stores. */
+template <class T, typename IO> struct JrArgs {
+    const DModel<double> *Mg;
+    const SModel<T, double> *Sg;
+    int n, flags, frame;
+    const IO *q, *u, *qdd, *ft, *ext;
+    IO *reaction, *point, *tau_joint, *muscle_wrench;
+};
+
+/* The point forces of one muscle at tendon force Ft, summed per composite
+ * body: wr[b] += ((P - o_b) x f, f) for every active path point on body b —
+ * the moment about the body's own origin (lever arms of a segment's length,
+ * not of the model's distance from the ground origin, which costs fp32 two
+ * digits in sums that cancel); the caller shifts each body's sum once.
+ * f = Ft (e_next - e_prev) = -Ft g in muscle_path's notation.  muscle_path's point loop and activity rule
+ * (conditional points out of range are skipped, moving points sit at their
+ * function values), without the moment arms; a moving point's g . dP/dq is a
+ * mobility force and is not formed.  The body index is matched by selects, so
+ * wr stays in registers. */
+template <bool BFK, class T, typename Real>
+DEV void muscle_point_wrench(const SModel<T, Real> &SM, const SMuscle<Real> &mu, const Real *lds, Real Ft,
+                             Real (&wr)[T::NB][6]) {
+    using LY = Lay<T, Real>;
+    constexpr bool BF = BFK;
+    const Real *ldsq = lds + LY::QF;
+    Real Pp[3] = {0, 0, 0}, rp[3] = {0, 0, 0}, ep[3] = {0, 0, 0};
+    int cbp = -1;
+    bool have = false;
+    auto flush = [&](const Real *g) {
+        Real f[3] = {-Ft * g[0], -Ft * g[1], -Ft * g[2]}, mo[3];
+        cross3(rp, f, mo);
+        sfor<0, T::NB>([&](auto bI) {
+            constexpr int b = decltype(bI)::value;
+            const bool on = cbp == b;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                wr[b][i] += on ? mo[i] : Real(0);
+                wr[b][3 + i] += on ? f[i] : Real(0);
+            }
+        });
+    };
+    const int npt = mu.npt;
+    constexpr int MP = T::MAXPT > 0 ? T::MAXPT : 1;
+    int cbj[MP];
+    bool onj[MP];
+    sfor<0, MP>([&](auto jI) {
+        constexpr int j = decltype(jI)::value;
+        const DPathPt<Real> &pt = SM.pt[mu.pt_off + (j < npt ? j : 0)];
+        cbj[j] = pt.cbody;
+        onj[j] = j < npt;
+        if constexpr (((T::PT_COND >> j) & 1u) != 0) {
+            const bool cnd = pt.type == BIOIM_PT_COND;
+            if constexpr (BF) {
+                const int ccd = pt.cond_coord, zero = 0;
+                const Real qc = ldsq[cnd ? ccd : zero], plo = pt.lo, phi = pt.hi;
+                onj[j] = onj[j] & !(cnd & ((qc < plo) | (qc > phi)));
+            } else {
+                const Real qc = ldsq[cnd ? pt.cond_coord : 0];
+                onj[j] = onj[j] && !(cnd && (qc < pt.lo || qc > pt.hi));
+            }
+        }
+    });
+    sfor<0, MP>([&](auto jI) {
+        constexpr int j = decltype(jI)::value;
+        const DPathPt<Real> &pt = SM.pt[mu.pt_off + (j < npt ? j : 0)];
+        if (onj[j]) {
+            Real loc[3] = {pt.loc[0], pt.loc[1], pt.loc[2]};
+            if constexpr (((T::PT_MOVING >> j) & 1u) != 0) {
+                if (pt.type == BIOIM_PT_MOVING) {
+                    Real ll[3];
+#pragma unroll
+                    for (int a = 0; a < 3; ++a) {
+                        const int f = pt.mf[a];
+                        ll[a] = f < 0 ? pt.loc[a] : lds[LY::MF + 3 * (f < 0 ? 0 : f)];
+                    }
+                    mv3(pt.R, ll, loc);
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) loc[i] += pt.p[i];
+                }
+            }
+            const Real *kbp = lds + LY::KB + 18 * cbj[j];
+            Real Rb[12];
+#pragma unroll
+            for (int i = 0; i < 12; ++i) Rb[i] = kbp[i];
+            Real P[3], r[3];
+            mv3(Rb, loc, r);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) P[i] = r[i] + Rb[9 + i];
+            Real e[3] = {0, 0, 0};
+            if (have) {
+                Real sgm[3] = {P[0] - Pp[0], P[1] - Pp[1], P[2] - Pp[2]};
+                const Real l2 = dot3(sgm, sgm);
+                const Real inv = fast_rsqrt(l2);
+#pragma unroll
+                for (int a = 0; a < 3; ++a) e[a] = sgm[a] * inv;
+                Real g[3] = {ep[0] - e[0], ep[1] - e[1], ep[2] - e[2]};
+                flush(g);
+            }
+#pragma unroll
+            for (int a = 0; a < 3; ++a) { ep[a] = e[a]; Pp[a] = P[a]; rp[a] = r[a]; }
+            cbp = cbj[j];
+            have = true;
+        }
+    });
+    if (have) flush(ep);
+}
+
+template <class T, typename IO>
+__global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_eu(1, 1))) void jr_kernel(JrArgs<T, IO> a) {
+    using Real = double;
+    using LY = Lay<T, Real>;
+    constexpr int G = T::G, ND = LY::ND, NB = T::NB, NM = T::NM, EPB = BIOIM_EPB;
+    constexpr size_t SMB = smodel_bytes<T, Real>();
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    {
+        const uint4 *src = reinterpret_cast<const uint4 *>(a.Sg);
+        uint4 *dst = reinterpret_cast<uint4 *>(smem_raw);
+        for (int i = threadIdx.x; i < (int)(SMB / 16); i += BIOIM_EPB * G) dst[i] = src[i];
+    }
+    __syncthreads();
+    const SModel<T, Real> &SM = *reinterpret_cast<const SModel<T, Real> *>(smem_raw);
+    const DModel<Real> &M = *a.Mg;
+    const int lane = threadIdx.x % G, slot = threadIdx.x / G;
+    const int idx = blockIdx.x * EPB + slot;
+    if (idx >= a.n) return;
+    Real *lds = reinterpret_cast<Real *>(smem_raw + SMB) + slot * LY::SIZE;
+    const bool contact = (a.flags & BIOIM_JR_CONTACT) != 0;
+    Real qd = 0, ud = 0, ad = 0;
+    if (lane < ND) {
+        qd = GAT(a.q, (size_t)idx * ND + lane, (size_t)a.n * ND);
+        ud = a.u ? GAT(a.u, (size_t)idx * ND + lane, (size_t)a.n * ND) : Real(0);
+        ad = a.qdd ? GAT(a.qdd, (size_t)idx * ND + lane, (size_t)a.n * ND) : Real(0);
+    }
+    publish_coords<T, Real>(M, SM, lds, lane, qd, ud);
+    if (lane < ND) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) lds[LY::SL + 6 * lane + i] = 0;
+    }
+    wave_sync();
+    Real x0 = 0;
+    if constexpr (T::TX >= 0) {
+        if constexpr (T::coord_dof[T::TX] >= 0) x0 = M.float_origin ? lds[LY::QF + T::TX] : Real(0);
+    }
+    fn_slots<false, T, Real>(SM, lds, lane);
+    if (lane < NB) kin_local<T, Real>(SM, lds, lane);
+    if (lane == NB) kin_ground<T, Real>(lds, x0);
+    wave_sync();
+    if (lane < NB) kin_chain<T, Real>(SM, lds, lane, x0);
+    wave_sync();
+    if (lane < ND) kin_column<T, Real>(SM, lds, lane);
+    if (lane < NB) body_inertia<T, Real>(SM, M, lds, lane);
+    if (lane < ND) lds[LY::RHS + lane] = ad;
+    wave_sync();   /* columns, inertias and wrenches are out; the joint-local region the CJ slots share is free */
+    if (contact && lane < T::NS) contact_lane<false, T, Real>(SM, lds, lane, Real(0));
+    /* the muscles' wrench on every body, in every lane (moment3, force3 about the shifted origin) */
+    Real mw[NB][6];
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int i = 0; i < 6; ++i) mw[b][i] = 0;
+    if constexpr (NM > 0) {
+        sfor<0, (NM + G - 1) / G>([&](auto jI) {
+            constexpr int j = decltype(jI)::value;
+            const int m = mslot<T>(lane + j * G);
+            if (m < NM) {
+                const Real Ft = a.ft ? GAT(a.ft, (size_t)idx * NM + m, (size_t)a.n * NM) : Real(0);
+                muscle_point_wrench<false, T, Real>(SM, SM.mus[m], lds, Ft, mw);
+            }
+        });
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+#pragma unroll
+            for (int i = 0; i < 6; ++i) mw[b][i] = group_sum<G>(mw[b][i]);
+    }
+    wave_sync();
+    Real mk[6] = {0, 0, 0, 0, 0, 0}, W[6] = {0, 0, 0, 0, 0, 0};
+    if (lane < NB) {
+        sfor<0, NB>([&](auto bI) {
+            constexpr int b = decltype(bI)::value;
+#pragma unroll
+            for (int i = 0; i < 6; ++i) mk[i] = lane == b ? mw[b][i] : mk[i];
+        });
+        {   /* from the body's own origin to the (shifted) ground origin */
+            Real ts[3];
+            cross3(lds + LY::KB + 18 * lane + 9, mk + 3, ts);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) mk[i] += ts[i];
+        }
+        /* spatial acceleration of the q'' on k's root path, then I_k a (the I S form of id_kernel) */
+        const unsigned dm = SM.dofmask[lane];
+        Real acc[6] = {0, 0, 0, 0, 0, 0}, t[3];
+        sfor<0, ND>([&](auto dI) {
+            constexpr int d = decltype(dI)::value;
+            const Real ddq = ((dm >> d) & 1u) ? lds[LY::RHS + d] : Real(0);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) acc[i] += lds[LY::S + 6 * d + i] * ddq;
+        });
+        const Real *ic = lds + LY::IC + 10 * lane, *wb = lds + LY::WB + 6 * lane;
+        symv(ic + 4, acc, W);
+        cross3(ic + 1, acc + 3, t);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) W[i] += t[i];
+        cross3(acc, ic + 1, t);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) W[3 + i] = ic[0] * acc[3 + i] + t[i];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) W[i] += wb[i];
+        if (contact) {
+            sfor<0, T::NS>([&](auto sI) {
+                constexpr int sp = decltype(sI)::value;
+                const bool on = SM.sph_cb[sp] == lane;
+                const Real *cw = lds + LY::CW + 8 * sp;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    W[i] -= on ? cw[3 + i] : Real(0);
+                    W[3 + i] -= on ? cw[i] : Real(0);
+                }
+            });
+        }
+        {   /* ext: fx fy fz mx my mz about the true ground origin, which sits at (-x0, 0, 0) here */
+            Real e[6] = {0, 0, 0, 0, 0, 0};
+            if (a.ext) {
+#pragma unroll
+                for (int i = 0; i < 6; ++i)
+                    e[i] = GAT(a.ext, ((size_t)idx * NB + lane) * 6 + i, (size_t)a.n * NB * 6);
+            }
+            W[0] -= e[3];
+            W[1] -= e[4] + x0 * e[2];
+            W[2] -= e[5] - x0 * e[1];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) W[3 + i] -= e[i];
+        }
+#pragma unroll
+        for (int i = 0; i < 6; ++i) W[i] -= mk[i];
+    }
+    wave_sync();
+    if (lane < NB) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) lds[LY::WB + 6 * lane + i] = W[i];
+    }
+    wave_sync();
+    Real F[6] = {0, 0, 0, 0, 0, 0};
+    if (lane < NB) {
+        sfor<0, NB>([&](auto dI) {
+            constexpr int d = decltype(dI)::value;
+            if ((T::anc[d] >> lane) & 1u) {
+#pragma unroll
+                for (int i = 0; i < 6; ++i) F[i] += lds[LY::WB + 6 * d + i];
+            }
+        });
+    }
+    wave_sync();
+    if (lane < NB) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) lds[LY::WB + 6 * lane + i] = F[i];
+    }
+    wave_sync();
+    if (lane < NB) {
+        const SBody<Real> &b = SM.body[lane];
+        const Real *kb = lds + LY::KB + 18 * lane;
+        /* c_b = o_b - R_b R_mb^T p_mb: the origin of the joint's child-side frame */
+        Real pm[3], c[3], t[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) pm[i] = b.R_mb[i] * b.p_mb[0] + b.R_mb[3 + i] * b.p_mb[1] + b.R_mb[6 + i] * b.p_mb[2];
+        mv3(kb, pm, c);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) c[i] = kb[9 + i] - c[i];
+        const size_t row = (size_t)idx * NB + lane, rows = (size_t)a.n * NB;
+        if (a.point) {
+            GAT(a.point, row * 3, rows * 3) = IO(c[0] + x0);
+            GAT(a.point, row * 3 + 1, rows * 3) = IO(c[1]);
+            GAT(a.point, row * 3 + 2, rows * 3) = IO(c[2]);
+        }
+        if (a.reaction) {
+            Real f[3] = {F[3], F[4], F[5]}, mo[3];
+            cross3(c, f, t);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) mo[i] = F[i] - t[i];
+            if (a.frame != BIOIM_JR_GROUND) {   /* ground -> frame: R^T */
+                const Real *Rf = lds + LY::KB + 18 * (a.frame == BIOIM_JR_CHILD ? lane : b.pslot);
+                Real fo[3], mq[3];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    fo[i] = Rf[i] * f[0] + Rf[3 + i] * f[1] + Rf[6 + i] * f[2];
+                    mq[i] = Rf[i] * mo[0] + Rf[3 + i] * mo[1] + Rf[6 + i] * mo[2];
+                }
+#pragma unroll
+                for (int i = 0; i < 3; ++i) { f[i] = fo[i]; mo[i] = mq[i]; }
+            }
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                GAT(a.reaction, row * 6 + i, rows * 6) = IO(f[i]);
+                GAT(a.reaction, row * 6 + 3 + i, rows * 6) = IO(mo[i]);
+            }
+        }
+        if (a.muscle_wrench) {   /* about the true ground origin: M + (x0, 0, 0) x f */
+            GAT(a.muscle_wrench, row * 6, rows * 6) = IO(mk[3]);
+            GAT(a.muscle_wrench, row * 6 + 1, rows * 6) = IO(mk[4]);
+            GAT(a.muscle_wrench, row * 6 + 2, rows * 6) = IO(mk[5]);
+            GAT(a.muscle_wrench, row * 6 + 3, rows * 6) = IO(mk[0]);
+            GAT(a.muscle_wrench, row * 6 + 4, rows * 6) = IO(mk[1] - x0 * mk[5]);
+            GAT(a.muscle_wrench, row * 6 + 5, rows * 6) = IO(mk[2] + x0 * mk[4]);
+        }
+    }
+    if (a.tau_joint && lane < ND) {
+        const Real *Sd = lds + LY::S + 6 * lane, *Fb = lds + LY::WB + 6 * SM.dof_cb[lane];
+        GAT(a.tau_joint, (size_t)idx * ND + lane, (size_t)a.n * ND) = IO(dot3(Sd, Fb) + dot3(Sd + 3, Fb + 3));
+    }
+}
+
 /* ---------------------------------------------------------------- kernel
  * Launch arguments of one env segment (one handle).  mode 0: env step
  * (optionally with in-kernel auto-reset); mode 1: reset the listed envs.
@@ -5349,6 +5686,13 @@ struct IkCall {   /* bioim_ik_solve's arguments (untyped), for Ops::ik_launch */
     int32_t *status;
 };
 
+struct JrCall {   /* bioim_joint_reaction's arguments (untyped), for Ops::jr_launch */
+    int n;
+    const void *q, *u, *qdd, *ft, *ext;
+    int flags, frame;
+    void *reaction, *point, *tau_joint, *muscle_wrench;
+};
+
 struct Ops {
     const char *topo;   /* the topology struct's name (fused-pair lookup) */
     int lanes;
@@ -5364,6 +5708,8 @@ struct Ops {
     void (*so_launch)(bioim_handle_t *, const StaticOptCall &);
     /* bioim_ik_solve's launcher (every topology); null for an fp32 handle (fp64 kernels only) */
     void (*ik_launch)(bioim_handle_t *, const IkCall &);
+    /* bioim_joint_reaction's launcher (every topology, both precisions); < 0: the fp64 image's upload failed */
+    int (*jr_launch)(bioim_handle_t *, const JrCall &);
     /* the fused rollout kernel's launcher; null where that instantiation is
      * left out (bioim_rollout then loops over `launch`) */
     void (*rollout)(bioim_handle_t *, const RolloutCall &);
@@ -5379,6 +5725,7 @@ struct bioim_handle {
     hipEvent_t ev_fork, ev_join;
     void *model;        /* DModel<Real> on device */
     void *smodel;       /* SModel<T, Real> on device (staged into LDS per workgroup) */
+    void *jr_model, *jr_smodel;   /* fp32 handles: the fp64 DModel / SModel of jr_kernel (null on fp64 handles) */
     void *state_buf;    /* one allocation for every SoA array */
     size_t state_bytes;
     void *dstate;       /* DState<Real> (host copy of pointers) */
@@ -5392,6 +5739,7 @@ struct bioim_handle {
     int rk;             /* integrator: 0 semi-implicit substeps (pack nsub), 1 RK-Merson (bioim_set_integrator) */
     double rk_acc;
     int rk_budget;      /* RK attempts per env per launch, 0: unbudgeted (bioim_set_rk_budget) */
+    int rk_budgeted;    /* a budget was set at some time: only then can an env be suspended mid-step */
     uint8_t *ready_out; /* caller's device buffer [n] or null */
     const uint8_t *active; /* caller's device buffer [n] or null (bioim_set_active_mask) */
     int last_group_fused; /* the last bioim_step_group with this handle first ran one fused launch */
@@ -5677,6 +6025,51 @@ template <class T> void ik_launch_impl(bioim_handle_t *h, const IkCall &c) {
     hipLaunchKernelGGL((ik_kernel<T, Real>), dim3((c.n + EPB - 1) / EPB), dim3(BIOIM_EPB * T::G), lds, h->stream, a);
 }
 
+/* fp32 handles: the fp64 DModel / SModel of jr_kernel, built from the pack
+ * and uploaded on the handle's first bioim_joint_reaction (that call blocks
+ * for the two copies; handles that never ask for joint reactions carry
+ * nothing); freed with the handle */
+template <class T> int jr_fp64_model(bioim_handle_t *h) {
+    if (h->jr_smodel) return 0;
+    constexpr size_t B = smodel_bytes<T, double>();
+    std::vector<unsigned char> img(B, 0);
+    build_smodel<T, double>(h->pack, *reinterpret_cast<SModel<T, double> *>(img.data()));
+    std::unique_ptr<DModel<double>> hm(new DModel<double>());
+    convert_model<double>(h->pack, *hm);
+    if (!h->jr_model) HIPCHK(hipMalloc(&h->jr_model, sizeof(DModel<double>)));
+    HIPCHK(hipMemcpy(h->jr_model, hm.get(), sizeof(DModel<double>), hipMemcpyHostToDevice));
+    void *sm = nullptr;
+    HIPCHK(hipMalloc(&sm, B));
+    if (hipMemcpy(sm, img.data(), B, hipMemcpyHostToDevice) != hipSuccess) {
+        hipFree(sm);
+        return fail(BIOIM_E_DEVICE, "bioim_joint_reaction: uploading the fp64 model image failed");
+    }
+    h->jr_smodel = sm;
+    return 0;
+}
+
+/* IO: the handle's precision (the caller's arrays); the kernel is fp64 either
+ * way, on the handle's own image (fp64 handle) or on its fp64 copy (fp32) */
+template <class T, typename IO> int jr_launch_impl(bioim_handle_t *h, const JrCall &c) {
+    constexpr int EPB = BIOIM_EPB;
+    constexpr bool own = std::is_same<IO, double>::value;
+    if constexpr (!own) {
+        if (const int rc = jr_fp64_model<T>(h)) return rc;
+    }
+    JrArgs<T, IO> a;
+    a.Mg = reinterpret_cast<const DModel<double> *>(own ? h->model : h->jr_model);
+    a.Sg = reinterpret_cast<const SModel<T, double> *>(own ? h->smodel : h->jr_smodel);
+    a.n = c.n; a.flags = c.flags; a.frame = c.frame;
+    a.q = reinterpret_cast<const IO *>(c.q); a.u = reinterpret_cast<const IO *>(c.u);
+    a.qdd = reinterpret_cast<const IO *>(c.qdd); a.ft = reinterpret_cast<const IO *>(c.ft);
+    a.ext = reinterpret_cast<const IO *>(c.ext);
+    a.reaction = reinterpret_cast<IO *>(c.reaction); a.point = reinterpret_cast<IO *>(c.point);
+    a.tau_joint = reinterpret_cast<IO *>(c.tau_joint); a.muscle_wrench = reinterpret_cast<IO *>(c.muscle_wrench);
+    constexpr size_t lds = lds_bytes<T, double, false>();
+    hipLaunchKernelGGL((jr_kernel<T, IO>), dim3((c.n + EPB - 1) / EPB), dim3(BIOIM_EPB * T::G), lds, h->stream, a);
+    return 0;
+}
+
 template <class T, typename Real> int upload_smodel(bioim_handle_t *h) {
     static_assert(lds_bytes<T, Real, true>() <= 163840, "LDS image + env regions exceed 160 KiB");
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&env_kernel<T, Real, false, false>),
@@ -5708,6 +6101,8 @@ template <class T, typename Real> int upload_smodel(bioim_handle_t *h) {
     if constexpr (std::is_same<Real, double>::value)
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&ik_kernel<T, double>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, double, false>()));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&jr_kernel<T, Real>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, double, false>()));
     constexpr size_t B = smodel_bytes<T, Real>();
     std::vector<unsigned char> img(B, 0);
     build_smodel<T, Real>(h->pack, *reinterpret_cast<SModel<T, Real> *>(img.data()));
@@ -5726,6 +6121,8 @@ template <class T> bool pick(const bioim_modelpack_t &p, int precision, Ops &ops
     ops.ma_launch = nullptr;
     ops.so_launch = nullptr;
     ops.ik_launch = precision == 64 ? &ik_launch_impl<T> : nullptr;
+    if (precision == 64) ops.jr_launch = &jr_launch_impl<T, double>;
+    else ops.jr_launch = &jr_launch_impl<T, float>;
     if constexpr (T::NM > 0) {
         if (precision == 64) ops.ma_launch = &ma_launch_impl<T, double>;
         else ops.ma_launch = &ma_launch_impl<T, float>;
@@ -6041,6 +6438,7 @@ int bioim_create(const bioim_modelpack_t *pack, int n_envs, int device, int prec
     h->env_offset = 0;
     h->pert_n = 0; h->pert_ob = -1;
     h->reset_tab = nullptr; h->reset_tab_on = 1; h->cache_live = 0;
+    h->jr_model = nullptr; h->jr_smodel = nullptr; h->rk_budgeted = 0;
     h->rollout_live = nullptr; h->last_rollout_fused = 0; h->last_rollout_group_fused = 0;
     h->planar = pack_is_planar(*pack) ? 1 : 0;
     h->act_stride = pack->nact; h->obs_stride = pack->obs_dim; h->info_stride = pack->info_dim;
@@ -6069,6 +6467,8 @@ int bioim_destroy(bioim_handle_t *h) {
     if (h->state_buf) hipFree(h->state_buf);
     if (h->model) hipFree(h->model);
     if (h->smodel) hipFree(h->smodel);
+    if (h->jr_model) hipFree(h->jr_model);
+    if (h->jr_smodel) hipFree(h->jr_smodel);
     if (h->pert_x) hipFree(h->pert_x);
     if (h->pert_y) hipFree(h->pert_y);
     if (h->reset_tab) hipFree(h->reset_tab);
@@ -6234,6 +6634,7 @@ int bioim_set_integrator(bioim_handle_t *h, int kind, double accuracy) {
 int bioim_set_rk_budget(bioim_handle_t *h, int attempts, uint8_t *ready_out) {
     if (!h || attempts < 0) return fail(BIOIM_E_ARG, "bioim_set_rk_budget: null handle or negative budget");
     h->rk_budget = attempts;
+    if (attempts > 0) h->rk_budgeted = 1;
     h->ready_out = ready_out;
     return 0;
 }
@@ -6481,6 +6882,26 @@ int bioim_ik_solve(bioim_handle_t *h, int n, int nm, const int32_t *marker_body,
     return 0;
 }
 
+int bioim_joint_reaction(bioim_handle_t *h, int n, const void *q, const void *u, const void *qdd, const void *ft,
+                         const void *ext, int flags, int frame, void *reaction, void *point, void *tau_joint,
+                         void *muscle_wrench) {
+    if (!h) return fail(BIOIM_E_ARG, "bioim_joint_reaction: null handle");
+    if (n < 0) return fail(BIOIM_E_ARG, "bioim_joint_reaction: negative n");
+    if (n > 0 && !q) return fail(BIOIM_E_ARG, "bioim_joint_reaction: null q");
+    if (ft && h->nmuscle <= 0) return fail(BIOIM_E_ARG, "bioim_joint_reaction: ft on a model without muscles");
+    if (flags & ~BIOIM_JR_CONTACT) return fail(BIOIM_E_ARG, "bioim_joint_reaction: unknown flag bits");
+    if (frame < BIOIM_JR_GROUND || frame > BIOIM_JR_PARENT)
+        return fail(BIOIM_E_ARG, "bioim_joint_reaction: frame must be BIOIM_JR_GROUND, _CHILD or _PARENT");
+    if (!reaction && !point && !tau_joint && !muscle_wrench)
+        return fail(BIOIM_E_ARG, "bioim_joint_reaction: no output requested");
+    if (n == 0) return 0;
+    HIPCHK(hipSetDevice(h->device));
+    const JrCall c{n, q, u, qdd, ft, ext, flags, frame, reaction, point, tau_joint, muscle_wrench};
+    if (const int rc = h->ops.jr_launch(h, c)) return rc;
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 int bioim_osim_report_dim(const bioim_handle_t *h) {
     if (!h) return fail(BIOIM_E_ARG, "null handle");
     return osim_report_dim(h->pack);
@@ -6496,6 +6917,21 @@ int bioim_osim(bioim_handle_t *h, int op, const int32_t *env_ids, int n, const v
     HIPCHK(hipSetDevice(h->device));
     const OsimCall oc{op, controls, report};
     h->ops.launch(h, 2, nullptr, obs, nullptr, nullptr, nullptr, env_ids, nullptr, n, &oc);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int bioim_realize_report(bioim_handle_t *h, const int32_t *env_ids, int n, void *report) {
+    if (!h) return fail(BIOIM_E_ARG, "bioim_realize_report: null handle");
+    if (n < 0) return fail(BIOIM_E_ARG, "bioim_realize_report: negative n");
+    if (n > 0 && !env_ids) return fail(BIOIM_E_ARG, "bioim_realize_report: null env_ids");
+    if (!report) return fail(BIOIM_E_ARG, "bioim_realize_report: null report");
+    if (h->rk_budgeted)
+        return fail(BIOIM_E_ARG, "bioim_realize_report: the handle has had an RK budget (envs may be suspended): use bioim_osim");
+    if (n == 0) return 0;
+    HIPCHK(hipSetDevice(h->device));
+    const OsimCall oc{BIOIM_OSIM_REALIZE, nullptr, report};
+    h->ops.launch(h, 2, nullptr, nullptr, nullptr, nullptr, nullptr, env_ids, nullptr, n, &oc);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -319,6 +319,87 @@ int bioim_ik_solve(bioim_handle_t *h, int n, int nm, const int32_t *marker_body 
                    double tol, int max_iter, void *q /* [n][ndof], required */, void *markers /* [n][nm][3] */,
                    void *err /* [n][2] */, void *jacobian /* [n][nm][3][ndof] */,
                    int32_t *status /* [n]: iterations used, or -1 cap hit, -2 factorization failed / NaN */);
+/* Joint reaction analysis (OpenSim's JointReaction, the fifth link of the
+ * chain after IK, InverseDynamics, MuscleAnalysis and StaticOptimization) on
+ * the handle's model, batched over n arbitrary states — not the handle's
+ * envs: the env state and the realize cache are neither read nor written.
+ * Per state, the resultant force and moment each composite body's inboard
+ * joint carries.  All pointers are device pointers in the handle's precision,
+ * dof order as for bioim_id_eval.  The arithmetic is fp64 on either handle: an
+ * fp32 handle keeps an fp64 image of the model for this call and converts at
+ * its loads and stores (a foot's contact force turns the 1e-7 m of an fp32
+ * kinematic chain into 0.1 N), so its results are the fp64 ones of its
+ * fp32 inputs, rounded.  That image is built and uploaded on an fp32 handle's
+ * first call, which blocks for the copy; no later call does.
+ *
+ * All definitions are per state, in the ground frame.  The sums run over
+ * composite bodies k (the pack's cbody, 5 or 7 per model).
+ * The wrench that body k's own balance leaves for its joints is
+ *     W_k = I_k a_k + v_k x* I_k v_k - (gravity on k)
+ *           - (Hunt-Crossley contact on k, if flag CONTACT)
+ *           - ext_k - (muscle point forces on k)
+ * Here a_k = AL_k + sum over the dofs d on k's root path of S_d q''_d.  AL
+ * holds the velocity-product accelerations the prologue already publishes,
+ * and S_d are the ground-frame Plucker columns.
+ * Reaction.  F_b = sum over k in subtree(b) of W_k is the wrench the parent
+ * (ground for the root) exerts on body b through b's inboard joint.  Its
+ * moment is taken about c_b = o_b - R_b R_mb^T p_mb, the origin of the
+ * joint's child-side frame M, which is o_b in every shipped pack.
+ * Muscle point forces.  For muscle m with tendon force Ft_m, take every
+ * active path point j with exactly muscle_path's activity rule:
+ *   - conditional points are out of range when q < lo || q > hi;
+ *   - moving points sit at their function values.
+ * The force on point j's body at P_j is Ft_m (e_{j->j+1} - e_{j-1->j}), where
+ * e is the unit segment directions and the end points have one term each.
+ * This is -Ft g in muscle_path's notation.
+ * A moving point's own-coordinate term (g . dP/dq, muscle_path's gd) is a
+ * mobility force, not a body force.  It is not part of F.
+ * Coordinate limit forces, coordinate actuators and reserves are mobility
+ * forces too.  They never enter this kernel.  They appear in tau_joint as
+ * what the coordinate itself must carry.
+ * Generalized force.  tau_joint_d = S_d . F_{cb(d)}, taken with Omega_d on
+ * the moment and V_d on the force, both about the same point.
+ *
+ *   q, u, qdd [n][ndof]          u, qdd NULL: zeros;
+ *   ft   [n][nmuscle]            tendon forces (bioim_muscle_eval's fiber
+ *                                column 2, or the REALIZE report's); NULL: no
+ *                                muscle forces, bit for bit as all zeros;
+ *   ext  [n][ncbody][6]          fx fy fz mx my mz applied to each body, ground
+ *                                frame, moment about the ground origin;
+ *   flags                        BIOIM_JR_CONTACT adds the model's Hunt-Crossley
+ *                                contact at (q, u) (the explicit force,
+ *                                bioim_id_eval's);
+ *   frame                        rotates `reaction` only: CHILD is body b's
+ *                                composite frame, PARENT the parent's composite
+ *                                frame (ground for the root).
+ * Outputs (any may be NULL, not all):
+ *   reaction      [n][ncbody][6]  fx fy fz mx my mz of F_b about c_b;
+ *   point         [n][ncbody][3]  c_b in the ground frame;
+ *   tau_joint     [n][ndof];
+ *   muscle_wrench [n][ncbody][6]  the muscles' net wrench on body k alone (not
+ *                                the subtree), ground frame, about the ground
+ *                                origin; zeros on a model without muscles.
+ * Planar models keep all six components: their hips sit off the plane, so mx,
+ * my (and a lateral force, where one acts) are loads the joints carry.
+ * Joints inside a composite body (welded or locked ones) have no row.
+ * A state's result does not depend on n or on the other states, and a
+ * repeated call repeats it bit for bit (the muscle forces are summed per body
+ * in a fixed order).  BIOIM_E_ARG, before any device call and in this order,
+ * for: a null handle, n < 0, null q with n > 0, ft on a model without
+ * muscles, unknown flag bits, frame outside 0..2, every output NULL.  n == 0
+ * returns BIOIM_OK without a launch.  Asynchronous on the handle's stream;
+ * synchronizes nothing.  No reference counterpart (the reference ships
+ * JointReaction results of its OpenSim runs, not the analysis). */
+enum { BIOIM_JR_GROUND = 0, BIOIM_JR_CHILD = 1, BIOIM_JR_PARENT = 2 };   /* frame the outputs are expressed in */
+#define BIOIM_JR_CONTACT 1                                               /* flags: add the model's contact at (q, u) */
+int bioim_joint_reaction(bioim_handle_t *h, int n, const void *q, const void *u /* NULL: 0 */,
+        const void *qdd /* NULL: 0 */, const void *ft /* [n][nmuscle] tendon forces, NULL: none */,
+        const void *ext /* [n][ncbody][6] fx fy fz mx my mz on each body, ground frame, moment about the ground origin; NULL: none */,
+        int flags, int frame,
+        void *reaction /* [n][ncbody][6]: fx fy fz mx my mz of F_b about c_b */,
+        void *point /* [n][ncbody][3]: c_b in the ground frame */,
+        void *tau_joint /* [n][ndof] */,
+        void *muscle_wrench /* [n][ncbody][6]: the muscles' net wrench on body k alone (not the subtree), ground frame, about the ground origin */);
 /* OsimModel calls on single envs (the reference's physics facade,
  * opensim_wrapper.py:92-332), for callers that drive the model directly
  * (tests/example_position_control.py:203-223; the env methods
@@ -361,6 +442,21 @@ enum {
 };
 int bioim_osim_report_dim(const bioim_handle_t *h);
 int bioim_osim(bioim_handle_t *h, int op, const int32_t *env_ids, int n, const void *controls, void *obs, void *report);
+/* The REALIZE report of the n listed envs (env_ids: device int32[n], distinct,
+ * in [0, N): the caller's contract) into report (device
+ * [N][bioim_osim_report_dim], rows indexed by env), as bioim_osim with op
+ * BIOIM_OSIM_REALIZE, no controls and no obs: the state is read, the next
+ * bioim_step's results stay bit for bit what they are without the call.
+ * Unlike bioim_osim it does not read the suspended-step flags back first, so
+ * it is asynchronous on the handle's stream and synchronizes nothing: the
+ * form for a per-step reward or constraint (VectorEnv.joint_reaction).  In
+ * exchange it is refused on a handle that was ever given an RK budget
+ * (bioim_set_rk_budget with attempts > 0), the only handles whose envs can be
+ * suspended mid-step; those use bioim_osim.  BIOIM_E_ARG, before any device
+ * call and in this order, for: a null handle, n < 0, null env_ids with n > 0,
+ * a null report, a handle that has had an RK budget.  n == 0 returns BIOIM_OK
+ * without a launch. */
+int bioim_realize_report(bioim_handle_t *h, const int32_t *env_ids, int n, void *report);
 /* Global index of this handle's env 0 (multi-GPU sharding): device-drawn
  * reset indices depend on the global env index, so a sharded run is
  * bit-identical to an unsharded one. */
