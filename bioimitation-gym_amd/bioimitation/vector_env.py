@@ -559,6 +559,45 @@ class VectorEnv:
             self._realize_sync = True     # the refusal is for the handle's lifetime
         return self.osim('realize', ids, want_obs=False)
 
+    def _own_state_inputs(self, env_ids, rows):
+        """What the analyses at the envs' own state start from (``joint_reaction``,
+        ``induced_accelerations``): (n, q, u, realize), with q and u from
+        the state rows (gathered on the device unless ``rows`` has them) and
+        ``realize()`` the REALIZE report rows of those envs, in their order,
+        cut by the report's layout (include/bioim.h: time, istep, q[nc], u[nc],
+        qdd[nc], 18 per OpenSim body, the COM's 9, 7 per muscle with the tendon
+        force last, then one per actuator) into a dict: 'qdd' [n][ndof],
+        'ft' [n][nmuscle] (None without muscles), 'act' [n][nact]."""
+        import torch
+        from .packdef import state_row_slices
+        pk = self.pack
+        host = None
+        if env_ids is None:
+            n, ids = self.num_envs, torch.arange(self.num_envs, dtype=torch.int32, device=self.device)
+        else:
+            host, ids = self._id_list(env_ids, 'env', distinct=True)
+            n = host.size
+        if rows is None:
+            rows = self.state_rows(env_ids=env_ids)
+        sl, _ = state_row_slices(pk.ndof, pk.nmuscle, pk.nact, pk.horizon)
+        q, u = (rows[:, sl[f]].to(self.dtype).contiguous() for f in ('q', 'u'))
+
+        def realize():
+            dev_ids = ids if ids is not None else self._upload_ids(host)
+            rep = self._realize_report(dev_ids, n).index_select(0, dev_ids.long())
+            if getattr(self, '_jr_dof_coord', None) is None:
+                coord_of = [c for d in range(pk.ndof) for c in range(pk.ncoord) if pk.coord[c].dof == d]
+                self._jr_dof_coord = torch.as_tensor(coord_of, dtype=torch.long).to(self.device, non_blocking=True)
+            k = 2 + 2 * pk.ncoord
+            out = dict(qdd=rep[:, k:k + pk.ncoord].index_select(1, self._jr_dof_coord).contiguous(), ft=None)
+            k = 2 + 3 * pk.ncoord + 18 * pk.nosbody + 9
+            if pk.nmuscle:
+                out['ft'] = rep[:, k:k + 7 * pk.nmuscle].reshape(n, pk.nmuscle, 7)[:, :, 6].contiguous()
+            k += 7 * pk.nmuscle
+            out['act'] = rep[:, k:k + pk.nact]
+            return out
+        return n, q, u, realize
+
     def joint_reaction(self, env_ids=None, frame='child', on='child', want=('reaction',), rows=None):
         """Joint reactions (``bioimitation.joint_reaction``) at the envs' own
         state: {key: device tensor} for the keys of ``want``, one row per env
@@ -575,42 +614,67 @@ class VectorEnv:
         suspended-step flags back, and a precision=32 env's first call uploads
         the fp64 model image.  ``rows``: state rows already gathered for these
         envs.  The result labels itself for ``joint_reaction.write_sto``."""
-        import torch
         from . import joint_reaction as jr
-        from .packdef import state_row_slices
         pk = self.pack
         jr.check_frame(frame, on)
-        if env_ids is None:
-            n, ids = self.num_envs, torch.arange(self.num_envs, dtype=torch.int32, device=self.device)
-        else:
-            host, ids = self._id_list(env_ids, 'env', distinct=True)
-            n = host.size
-        if rows is None:
-            rows = self.state_rows(env_ids=env_ids)
-        sl, _ = state_row_slices(pk.ndof, pk.nmuscle, pk.nact, pk.horizon)
-        q, u = (rows[:, sl[f]].to(self.dtype).contiguous() for f in ('q', 'u'))
+        n, q, u, realize = self._own_state_inputs(env_ids, rows)
         _, want = jr.check_args(pk.ndof, pk.nmuscle, pk.ncbody, q, u, want=want, frame=frame, on=on)
         if q.shape[0] != n:
             raise ValueError(f'joint_reaction: rows has {q.shape[0]} rows for {n} envs')
         qdd = ft = None
         if n:
-            if ids is None:
-                ids = self._upload_ids(host)
-            rep = self._realize_report(ids, n).index_select(0, ids.long())
-            # report layout (include/bioim.h): time, istep, q[nc], u[nc], qdd[nc], 18 per OpenSim body, the COM's 9,
-            # then 7 per muscle, the tendon force last
-            if getattr(self, '_jr_dof_coord', None) is None:
-                coord_of = [c for d in range(pk.ndof) for c in range(pk.ncoord) if pk.coord[c].dof == d]
-                self._jr_dof_coord = torch.as_tensor(coord_of, dtype=torch.long).to(self.device, non_blocking=True)
-            k = 2 + 2 * pk.ncoord
-            qdd = rep[:, k:k + pk.ncoord].index_select(1, self._jr_dof_coord).contiguous()
-            if pk.nmuscle:
-                k = 2 + 3 * pk.ncoord + 18 * pk.nosbody + 9
-                ft = rep[:, k:k + 7 * pk.nmuscle].reshape(n, pk.nmuscle, 7)[:, :, 6].contiguous()
+            rep = realize()
+            qdd, ft = rep['qdd'], rep['ft']
         if getattr(self, '_jr_table', None) is None:
             self._jr_table = jr.JointTable(self.env_id)
         res = jr.Result(jr.launch(self, q, u, qdd, ft, None, True, frame, on, want))
         res.table, res.frame, res.on = self._jr_table, frame, on
+        return res
+
+    def induced_accelerations(self, env_ids=None, kind='point', want=('accel',), force_threshold=0.0, rows=None):
+        """Induced accelerations (``bioimitation.induced_accelerations``) at
+        the envs' own state: {key: device tensor} for the keys of ``want``,
+        one row per env (or per listed env, in the list's order; distinct
+        ids), one column per contributor.  Built like ``joint_reaction``: q and
+        u are gathered on the device (``state_rows``); the muscles' tendon
+        forces and the actuators' forces come from a REALIZE report of those
+        envs (``bioim_realize_report``, which leaves their next step bit for
+        bit what it is without it), the actuator forces mapped to the dofs
+        through the pack's coordinate-actuator table; then one
+        ``bioim_induced_accel`` launch in which the model itself decides which
+        feet are held (``kind='point'``, ``force_threshold``).  All of it is
+        enqueued on the env's stream: no host round trip and no
+        synchronization (an env that has had an RK budget realizes through
+        ``osim``, which reads its suspended-step flags back).  fp64 envs only.
+        ``rows``: state rows already gathered for these envs."""
+        import torch
+        from . import induced_accelerations as ia
+        pk = self.pack
+        ia.check_env(self)
+        n, q, u, realize = self._own_state_inputs(env_ids, rows)
+        _, want = ia.check_args(pk.ndof, pk.nmuscle, pk.ncbody, pk.ncforce, q, u, kind=kind,
+                                force_threshold=force_threshold, want=want)
+        if q.shape[0] != n:
+            raise ValueError(f'induced_accelerations: rows has {q.shape[0]} rows for {n} envs')
+        ft = tau_act = None
+        if n:
+            rep = realize()
+            ft = rep['ft']
+            if pk.ncoordact:
+                if getattr(self, '_ia_act_dof', None) is None:
+                    # [nact][ndof] 0 / 1: coordinate actuator a drives dof coordact[a].dof (none: a locked coordinate)
+                    m = np.zeros((pk.nact, pk.ndof))
+                    for a in range(pk.ncoordact):
+                        if pk.coordact[a].dof >= 0:
+                            m[a, pk.coordact[a].dof] = 1.0
+                    self._ia_act_dof = torch.as_tensor(m).to(device=self.device, dtype=self.dtype, non_blocking=True)
+                tau_act = (rep['act'] @ self._ia_act_dof).contiguous()
+        res = ia.Result(ia.launch(self, q, u, ft, tau_act, None, kind, None, None, force_threshold, want))
+        if getattr(self, '_ia_names', None) is None:
+            from .obslayout import load_names
+            names = load_names(self.env_id)
+            self._ia_names = (ia.contributor_names(pk, names), ia.dof_names(pk, names))
+        (res.contributors, res.coords), res.kind = self._ia_names, kind
         return res
 
     def load_state(self, rows, env_ids=None):

@@ -3818,6 +3818,528 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_e
     }
 }
 
+/* ---------------------------------------------------- induced accelerations
+ * bioim_induced_accel (include/bioim.h): per state the share of every
+ * coordinate's acceleration, of the mass centre's acceleration and of every
+ * foot's ground reaction that is due to gravity, to the velocity terms, to each
+ * contact force, the limit forces, the caller's actuator and external forces,
+ * and to each single muscle: one column per contributor, the last their total.
+ * fp64 only (M^-1 and a Schur complement on a floating base).
+ *
+ * The other analysis kernels' shape: one state per G lanes, the model image in
+ * LDS, then the env regions of Lay (unchanged), then this kernel's private
+ * tail (IaLay), one per state.  The tail does not fit beside 16 env regions on
+ * the spatial muscle topologies, so IaLay::EPB states share a workgroup: 16
+ * where that fits into 160 KiB, 8 elsewhere.
+ *   1. id_kernel's prologue through body_inertia; body lanes split the
+ *      gravity wrench off WB (WG) and stage ext (XW, moved to the shifted
+ *      origin, jr_kernel's form); subtree sums of IC, WB, WG, XW, and the mass
+ *      centre's velocity-product acceleration sum_b m_b ac_b (lane NB);
+ *      contact_lane at h = 0, the limit lanes, the packed M.
+ *   2. POINT: foot lane f decides (cactive / cpoint, or sum fn_s > threshold
+ *      and P_f = sum fn_s P_s / sum fn_s over its active spheres, sphere order).
+ *   3. Dof lane d writes entry d of the gravity, velocity, contact, limit,
+ *      actuator and external columns and of the J rows; muscle lanes run
+ *      muscle_path by mslot and write their own column -Ft dL/dq; foot lanes
+ *      form beta_f.  Then the total column (fixed order).
+ *   4. M = L L^T in place in LDS (so_kernel's right-looking form on the lanes);
+ *      lane l substitutes the columns l, l + G, ... (the J^T columns too: Y),
+ *      reading L by broadcast.
+ *   5. POINT: S = J Y (+ identity on the rows of feet not held), its Cholesky
+ *      on lane 0, then per column lambda = -S^-1 (J A + beta), A += Y lambda.
+ *   6. com_accel per column from J_com (subtree mass and first moment times
+ *      the Plucker columns), then the stores; accel is one contiguous copy.
+ * A pivot <= 0 or a NaN (M, S, or the total column) gives status -2 and zero
+ * outputs.  No atomics, no shared slot written at a run-time index (a lane
+ * writes only columns it owns), every sum in a fixed order. */
+template <class T, typename Real> struct IaArgs {
+    const DModel<Real> *Mg;
+    const SModel<T, Real> *Sg;
+    int n, kind;
+    Real thr;
+    const Real *q, *u, *ft, *tau_act, *ext, *cpoint;
+    const uint8_t *cactive;
+    Real *accel, *com_accel, *reaction, *cpoint_out;
+    uint8_t *cactive_out;
+    int32_t *status;
+};
+
+template <class T, typename Real> struct IaLay {
+    using LY = Lay<T, Real>;
+    static constexpr int ND = LY::ND, NB = T::NB, NF = T::NF, NM = T::NM;
+    static constexpr int NCOL = 6 + NF + NM;         /* contributors (include/bioim.h order)          */
+    static constexpr int NR = T::PLANAR ? 2 : 3;     /* constraint rows per foot                      */
+    static constexpr int NJ = NF * NR, NX = NCOL + NJ;
+    static constexpr int COL = 0;                    /* [NX][ND]: Q_c then A_c; rows NCOL..: J^T then Y */
+    static constexpr int D = COL + NX * ND;          /* [ND] reciprocal pivots of M                   */
+    static constexpr int JR = D + ND;                /* [NJ][ND] J rows                               */
+    static constexpr int SS = JR + NJ * ND;          /* [NJ][NJ] S, then its factor (lower)           */
+    static constexpr int SD = SS + NJ * NJ;          /* [NJ] reciprocal pivots of S                   */
+    static constexpr int BETA = SD + NJ;             /* [NJ]                                          */
+    static constexpr int WG = BETA + NJ;             /* [NB][6] gravity wrenches; in place: subtree sums */
+    static constexpr int XW = WG + 6 * NB;           /* [NB][6] ext wrenches; in place: subtree sums  */
+    static constexpr int JC = XW + 6 * NB;           /* [3][ND] mass-centre Jacobian                  */
+    static constexpr int CB = JC + 3 * ND;           /* [3] sum m_b ac_b, [1] total mass              */
+    static constexpr int PF = CB + 4;                /* [NF][4]: P_f (shifted origin), held (0 / 1)   */
+    static constexpr int FLAG = PF + 4 * NF;         /* [1] S factored (0 / 1)                        */
+    static constexpr int SIZE = ((FLAG + 1 + 1) / 2) * 2;
+    static constexpr size_t bytes(int epb) {
+        return smodel_bytes<T, Real>() + (size_t)epb * (LY::SIZE + SIZE) * sizeof(Real);
+    }
+    static constexpr int EPB = bytes(BIOIM_EPB) <= 163840 ? BIOIM_EPB : BIOIM_EPB / 2;
+    static constexpr size_t lds_bytes = bytes(EPB);
+    static_assert(lds_bytes <= 163840, "LDS image + env regions + induced-acceleration tails exceed 160 KiB");
+    /* the composite body that carries force f's spheres */
+    static constexpr int foot_cb(int f) {
+        for (int s = 0; s < T::NS; ++s)
+            if (T::sphere_force[s] == f) return T::sphere_cb[s];
+        return 0;
+    }
+    static constexpr bool one_body_per_force() {
+        for (int s = 0; s < T::NS; ++s)
+            if (T::sphere_cb[s] != foot_cb(T::sphere_force[s])) return false;
+        return true;
+    }
+    static_assert(one_body_per_force(), "a contact force's spheres sit on one composite body");
+};
+
+template <class T, typename Real>
+__global__ __launch_bounds__((IaLay<T, Real>::EPB * T::G)) __attribute__((amdgpu_waves_per_eu(1, 1))) void ia_kernel(IaArgs<T, Real> a) {
+    using LY = Lay<T, Real>;
+    using IA = IaLay<T, Real>;
+    using PL = Planar<T>;
+    constexpr int G = T::G, ND = LY::ND, NB = T::NB, NM = T::NM, NF = T::NF, EPB = IA::EPB;
+    constexpr int NCOL = IA::NCOL, NR = IA::NR, NJ = IA::NJ;
+    constexpr int C_CON = 2, C_LIM = 2 + NF, C_ACT = 3 + NF, C_EXT = 4 + NF, C_MUS = 5 + NF, C_TOT = NCOL - 1;
+    constexpr size_t SMB = smodel_bytes<T, Real>();
+    static_assert(NB < G && NF <= G && NJ <= G, "body, foot and constraint-row lanes");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    {
+        const uint4 *src = reinterpret_cast<const uint4 *>(a.Sg);
+        uint4 *dst = reinterpret_cast<uint4 *>(smem_raw);
+        for (int i = threadIdx.x; i < (int)(SMB / 16); i += EPB * G) dst[i] = src[i];
+    }
+    __syncthreads();
+    const SModel<T, Real> &SM = *reinterpret_cast<const SModel<T, Real> *>(smem_raw);
+    const DModel<Real> &M = *a.Mg;
+    const int lane = threadIdx.x % G, slot = threadIdx.x / G;
+    const int idx = blockIdx.x * EPB + slot;
+    if (idx >= a.n) return;
+    Real *lds = reinterpret_cast<Real *>(smem_raw + SMB) + slot * LY::SIZE;
+    Real *tl = reinterpret_cast<Real *>(smem_raw + SMB) + EPB * LY::SIZE + slot * IA::SIZE;
+    const bool point = a.kind == BIOIM_IA_POINT;
+    Real qd = 0, ud = 0;
+    if (lane < ND) {
+        qd = GAT(a.q, (size_t)idx * ND + lane, (size_t)a.n * ND);
+        ud = a.u ? GAT(a.u, (size_t)idx * ND + lane, (size_t)a.n * ND) : Real(0);
+    }
+    publish_coords<T, Real>(M, SM, lds, lane, qd, ud);
+    if (lane < ND) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) lds[LY::SL + 6 * lane + i] = 0;
+    }
+    wave_sync();
+    Real x0 = 0;
+    if constexpr (T::TX >= 0) {
+        if constexpr (T::coord_dof[T::TX] >= 0) x0 = M.float_origin ? lds[LY::QF + T::TX] : Real(0);
+    }
+    constexpr bool BFK = T::PLANAR || BIOIM_BF_SPATIAL, BF3 = !T::PLANAR;
+    constexpr bool BFK_FN = BFK || (BF3 && (BIOIM_BF3 & 1)), BFK_PATH = BFK || (BF3 && (BIOIM_BF3 & 2));
+    fn_slots<(NM > 0 ? BFK_FN : false), T, Real>(SM, lds, lane);
+    if (lane < NB) kin_local<T, Real>(SM, lds, lane);
+    if (lane == NB) kin_ground<T, Real>(lds, x0);
+    wave_sync();
+    if (lane < NB) kin_chain<T, Real>(SM, lds, lane, x0);
+    wave_sync();
+    if (lane < ND) kin_column<T, Real>(SM, lds, lane);
+    if (lane < NB) {
+        body_inertia<T, Real>(SM, M, lds, lane);
+        /* the gravity wrench out of WB (id_kernel's CORIOLIS form) into WG; ext about the shifted origin into XW */
+        const Real *kb = lds + LY::KB + 18 * lane;
+        Real cG[3], mg[3], t[3];
+        mv3(kb, SM.body[lane].com, cG);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { cG[i] += kb[9 + i]; mg[i] = SM.body[lane].mass * M.gravity[i]; }
+        cross3(cG, mg, t);
+        Real *wb = lds + LY::WB + 6 * lane, *wg = tl + IA::WG + 6 * lane, *xw = tl + IA::XW + 6 * lane;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { wb[i] += t[i]; wb[3 + i] += mg[i]; wg[i] = t[i]; wg[3 + i] = mg[i]; }
+        Real e[6] = {0, 0, 0, 0, 0, 0};
+        if (a.ext) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) e[i] = GAT(a.ext, ((size_t)idx * NB + lane) * 6 + i, (size_t)a.n * NB * 6);
+        }
+        xw[0] = e[3];
+        xw[1] = e[4] + x0 * e[2];
+        xw[2] = e[5] - x0 * e[1];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) xw[3 + i] = e[i];
+    }
+    wave_sync();
+    {   /* subtree sums (all reads, then all writes); lane NB: sum_b m_b ac_b and the total mass */
+        Real ic[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, wb[6] = {0, 0, 0, 0, 0, 0}, wg[6] = {0, 0, 0, 0, 0, 0};
+        Real xw[6] = {0, 0, 0, 0, 0, 0}, cb[4] = {0, 0, 0, 0};
+        if (lane < NB) {
+            sfor<0, NB>([&](auto dI) {
+                constexpr int d = decltype(dI)::value;
+                if ((T::anc[d] >> lane) & 1u) {
+#pragma unroll
+                    for (int i = 0; i < 10; ++i) ic[i] += lds[LY::IC + 10 * d + i];
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) {
+                        wb[i] += lds[LY::WB + 6 * d + i];
+                        wg[i] += tl[IA::WG + 6 * d + i];
+                        xw[i] += tl[IA::XW + 6 * d + i];
+                    }
+                }
+            });
+        } else if (lane == NB) {
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+#pragma unroll
+                for (int i = 0; i < 3; ++i) cb[i] += lds[LY::WB + 6 * b + 3 + i];
+                cb[3] += lds[LY::IC + 10 * b];
+            }
+        }
+        wave_sync();
+        if (lane < NB) {
+#pragma unroll
+            for (int i = 0; i < 10; ++i) lds[LY::IC + 10 * lane + i] = ic[i];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                lds[LY::WB + 6 * lane + i] = wb[i];
+                tl[IA::WG + 6 * lane + i] = wg[i];
+                tl[IA::XW + 6 * lane + i] = xw[i];
+            }
+        } else if (lane == NB) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) tl[IA::CB + i] = cb[i];
+        }
+    }
+    if (lane < T::NS) contact_lane<false, T, Real>(SM, lds, lane, Real(0));
+    if (lane < T::NL) {
+        const int cc = SM.lim_coord[lane];
+        const Real qv = lds[LY::QF + cc], qdv = lds[LY::UF + cc];
+        const Real qup = SM.lim_qup[lane], qlo = SM.lim_qlow[lane], tr = SM.lim_trans[lane];
+        const Real itr = SM.lim_itrans[lane];
+        const Real up = smooth_step<false>(Real(0), Real(1), qup, qup + tr, itr, qv);
+        const Real lo = smooth_step<false>(Real(1), Real(0), qlo - tr, qlo, itr, qv);
+        lds[LY::LIM + 4 * lane] = -SM.lim_kup[lane] * up * (qv - qup) + SM.lim_klow[lane] * lo * (qlo - qv) -
+                                  SM.lim_damp[lane] * (up + lo) * qdv;
+    }
+    wave_sync();
+    if (lane < ND) {   /* row lane of the packed lower M (id_kernel's form) */
+        const Real *Sd = lds + LY::S + 6 * lane, *ic = lds + LY::IC + 10 * SM.dof_cb[lane];
+        Real Gk[6], t[3];
+        symv(ic + 4, Sd, Gk);
+        cross3(ic + 1, Sd + 3, t);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) Gk[i] += t[i];
+        cross3(Sd, ic + 1, t);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) Gk[3 + i] = ic[0] * Sd[3 + i] + t[i];
+        unsigned path = 0;
+        sfor<0, ND>([&](auto kI) {
+            constexpr int k = decltype(kI)::value;
+            constexpr unsigned pm = DofTree<T>::path_mask(k);
+            path = lane == k ? pm : path;
+        });
+        Real *row = lds + LY::MP + (lane * (lane + 1)) / 2;
+        sfor<0, ND>([&](auto lI) {
+            constexpr int l = decltype(lI)::value;
+            if (l <= lane) {
+                const Real *Sl = lds + LY::S + 6 * l;
+                row[l] = ((path >> l) & 1u) ? dot3(Sl, Gk) + dot3(Sl + 3, Gk + 3) : Real(0);
+            }
+        });
+        /* mass-centre Jacobian column: (Omega_d x h + m V_d) / m_total over the subtree dof d moves */
+        Real jc[3];
+        cross3(Sd, ic + 1, jc);
+        const Real im = Real(1) / tl[IA::CB + 3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) tl[IA::JC + i * ND + lane] = (jc[i] + ic[0] * Sd[3 + i]) * im;
+    }
+    if (lane < NF) {   /* which feet are held, and where */
+        Real fs = 0, Ps[3] = {0, 0, 0};
+        sfor<0, T::NS>([&](auto sI) {
+            constexpr int sp = decltype(sI)::value;
+            const bool on = T::sphere_force[sp] == lane && lds[LY::CW + 8 * sp + 6] > 0;
+            const Real fnv = lds[LY::CW + 8 * sp + 1];
+            const Real fn = on ? fnv : Real(0);
+            fs += fn;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) Ps[i] += fn * lds[LY::CJ + LY::CJN * sp + i];
+        });
+        bool held = false;
+        Real Pf[3] = {0, 0, 0};
+        if (point) {
+            if (a.cactive) {
+                held = GAT(a.cactive, (size_t)idx * NF + lane, (size_t)a.n * NF) != 0;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) Pf[i] = GAT(a.cpoint, ((size_t)idx * NF + lane) * 3 + i, (size_t)a.n * NF * 3);
+                Pf[0] -= x0;
+            } else {
+                held = fs > a.thr;
+                const Real inv = Real(1) / (held ? fs : Real(1));
+#pragma unroll
+                for (int i = 0; i < 3; ++i) Pf[i] = Ps[i] * inv;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) tl[IA::PF + 4 * lane + i] = held ? Pf[i] : Real(0);
+        tl[IA::PF + 4 * lane + 3] = held ? Real(1) : Real(0);
+    }
+    wave_sync();   /* M, J_com, the feet; CW / CJ / LIM are out */
+    if (lane < ND) {
+        const Real *Sd = lds + LY::S + 6 * lane;
+        const int cb = SM.dof_cb[lane];
+        const Real *wb = lds + LY::WB + 6 * cb, *wg = tl + IA::WG + 6 * cb, *xw = tl + IA::XW + 6 * cb;
+        Real *col = tl + IA::COL + lane;
+        col[0] = dot3(Sd, wg) + dot3(Sd + 3, wg + 3);
+        col[ND] = -(dot3(Sd, wb) + dot3(Sd + 3, wb + 3));
+        Real fc[NF];
+#pragma unroll
+        for (int f = 0; f < NF; ++f) fc[f] = 0;
+        sfor<0, T::NS>([&](auto sI) {
+            constexpr int sp = decltype(sI)::value;
+            constexpr unsigned msk = T::dofmask[T::sphere_cb[sp]];
+            const Real *cj = lds + LY::CJ + LY::CJN * sp;
+            Real jd[3];
+            contact_jac(Sd, cj, jd);
+            const Real term = dot3(jd, cj + 3);
+            fc[T::sphere_force[sp]] += (lds[LY::CW + 8 * sp + 6] > 0 && ((msk >> lane) & 1u)) ? term : Real(0);
+        });
+        sfor<0, NF>([&](auto fI) {
+            constexpr int f = decltype(fI)::value;
+            constexpr unsigned msk = T::dofmask[IA::foot_cb(f)];
+            const bool held = tl[IA::PF + 4 * f + 3] > 0;
+            col[(C_CON + f) * ND] = held ? Real(0) : fc[f];
+            /* J_f: (Omega_d x P_f + V_d) over the dofs that move the foot */
+            Real sc[6], jd[3];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) sc[i] = Sd[i];
+            PL::col(sc);
+            contact_jac(sc, tl + IA::PF + 4 * f, jd);
+            const bool on = held && ((msk >> lane) & 1u);
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+                const Real v = on ? jd[r] : Real(0);
+                tl[IA::JR + (f * NR + r) * ND + lane] = v;
+                col[(NCOL + f * NR + r) * ND] = v;
+            }
+        });
+        Real lim = 0;
+#pragma unroll
+        for (int li = 0; li < T::NL; ++li)
+            if (SM.lim_dof[li] == lane) lim += lds[LY::LIM + 4 * li];
+        col[C_LIM * ND] = lim;
+        col[C_ACT * ND] = a.tau_act ? GAT(a.tau_act, (size_t)idx * ND + lane, (size_t)a.n * ND) : Real(0);
+        col[C_EXT * ND] = dot3(Sd, xw) + dot3(Sd + 3, xw + 3);
+    }
+    if (lane < NF) {
+        /* beta_f: the acceleration of the body-fixed point at P_f along q + u t,
+         * aO + alpha x P + w x (vO + w x P) of the foot's body */
+        int fb = 0;
+        sfor<0, NF>([&](auto fI) {
+            constexpr int f = decltype(fI)::value;
+            fb = lane == f ? IA::foot_cb(f) : fb;
+        });
+        Real K[18], A[6], P[3], t[3], v[3], t2[3];
+#pragma unroll
+        for (int i = 0; i < 18; ++i) K[i] = lds[LY::KB + 18 * fb + i];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) A[i] = lds[LY::AL + 6 * fb + i];
+        PL::frame(K); PL::acc(A);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) P[i] = tl[IA::PF + 4 * lane + i];
+        const bool held = tl[IA::PF + 4 * lane + 3] > 0;
+        cross3(K + 12, P, t);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) v[i] = K[15 + i] + t[i];
+        cross3(A, P, t);
+        cross3(K + 12, v, t2);
+#pragma unroll
+        for (int r = 0; r < NR; ++r) tl[IA::BETA + lane * NR + r] = held ? A[3 + r] + t[r] + t2[r] : Real(0);
+    }
+    if constexpr (NM > 0) {
+        constexpr int NSP = T::MAXSPAN;
+        sfor<0, (NM + G - 1) / G>([&](auto jI) {
+            constexpr int j = decltype(jI)::value;
+            const int m = mslot<T>(lane + j * G);
+            if (m < NM) {
+                const SMuscle<Real> &mu = SM.mus[m];
+                Real L, dLs[NSP];
+                muscle_path<BFK_PATH, T, Real>(SM, mu, lds, L, dLs);
+                const Real nFt = a.ft ? -GAT(a.ft, (size_t)idx * NM + m, (size_t)a.n * NM) : Real(0);
+                Real *col = tl + IA::COL + (C_MUS + m) * ND;   /* this lane's own column */
+#pragma unroll
+                for (int d = 0; d < ND; ++d) {
+                    Real v = 0;
+#pragma unroll
+                    for (int k = 0; k < NSP; ++k) v = (k < mu.nspan && mu.span[k] == d) ? nFt * dLs[k] : v;
+                    col[d] = v;
+                }
+            }
+        });
+    }
+    wave_sync();
+    if (lane < ND) {
+        Real s = 0;
+#pragma unroll
+        for (int c = 0; c < C_TOT; ++c) s += tl[IA::COL + c * ND + lane];
+        tl[IA::COL + C_TOT * ND + lane] = s;
+    }
+    wave_sync();
+    /* M = L L^T in place (strict lower part scaled, reciprocal pivots in D).
+     * From here on `ok` differs between the states of one wave (it is uniform
+     * over a state's G lanes), so the syncs inside its regions are the
+     * lane-divergent form */
+    bool ok = true;
+    for (int k = 0; k < ND && ok; ++k) {
+        const Real piv = lds[LY::MP + k * (k + 1) / 2 + k];
+        ok = piv > Real(0);
+        if (ok) {
+            const Real rp = Real(1) / sqrt(piv);
+            for (int i = k + 1 + lane; i < ND; i += G) lds[LY::MP + i * (i + 1) / 2 + k] *= rp;
+            if (lane == 0) tl[IA::D + k] = rp;
+            wave_sync_lanes();
+            for (int i = k + 1 + lane; i < ND; i += G) {
+                Real *ri = lds + LY::MP + i * (i + 1) / 2;
+                const Real lik = ri[k];
+                for (int jc = k + 1; jc <= i; ++jc) ri[jc] -= lik * lds[LY::MP + jc * (jc + 1) / 2 + k];
+            }
+            wave_sync_lanes();
+        }
+    }
+    const int nx = point ? IA::NX : NCOL;
+    if (ok) {
+        /* lane l: columns l, l + G, ...: L y = b, then L^T x = y, in place */
+        for (int c = lane; c < nx; c += G) {
+            Real *x = tl + IA::COL + c * ND;
+            for (int k = 0; k < ND; ++k) {
+                const Real *rk = lds + LY::MP + k * (k + 1) / 2;
+                Real s = x[k];
+                for (int j = 0; j < k; ++j) s -= rk[j] * x[j];
+                x[k] = s * tl[IA::D + k];
+            }
+            for (int k = ND - 1; k >= 0; --k) {
+                Real s = x[k];
+                for (int i = k + 1; i < ND; ++i) s -= lds[LY::MP + i * (i + 1) / 2 + k] * x[i];
+                x[k] = s * tl[IA::D + k];
+            }
+        }
+    }
+    wave_sync();
+    if (ok) {   /* a NaN that came in (u, ft, tau_act, ext) shows in the total column */
+        const Real tv = lane < ND ? tl[IA::COL + C_TOT * ND + lane] : Real(0);
+        ok = !(group_max<G>((tv == tv) ? Real(0) : Real(1)) > Real(0));
+    }
+    if (ok && point) {
+        if (lane < NJ) {   /* row lane of S = J Y; a foot not held keeps the identity */
+            const bool held = tl[IA::PF + 4 * (lane / NR) + 3] > 0;
+            for (int i = 0; i < NJ; ++i) {
+                Real s = (i == lane && !held) ? Real(1) : Real(0);
+                for (int d = 0; d < ND; ++d) s += tl[IA::JR + lane * ND + d] * tl[IA::COL + (NCOL + i) * ND + d];
+                tl[IA::SS + lane * NJ + i] = s;
+            }
+        }
+        wave_sync_lanes();
+        if (lane == 0) {   /* NJ <= 6: the lower triangle, in place */
+            bool oks = true;
+            for (int k = 0; k < NJ; ++k) {
+                Real s = tl[IA::SS + k * NJ + k];
+                for (int j = 0; j < k; ++j) s -= tl[IA::SS + k * NJ + j] * tl[IA::SS + k * NJ + j];
+                oks = oks && s > Real(0);
+                const Real rp = Real(1) / sqrt(s > Real(0) ? s : Real(1));
+                tl[IA::SD + k] = rp;
+                for (int i = k + 1; i < NJ; ++i) {
+                    Real v = tl[IA::SS + i * NJ + k];
+                    for (int j = 0; j < k; ++j) v -= tl[IA::SS + i * NJ + j] * tl[IA::SS + k * NJ + j];
+                    tl[IA::SS + i * NJ + k] = v * rp;
+                }
+            }
+            tl[IA::FLAG] = oks ? Real(1) : Real(0);
+        }
+        wave_sync_lanes();
+        ok = tl[IA::FLAG] > Real(0);
+    }
+    const size_t crow = (size_t)idx * NCOL, crows = (size_t)a.n * NCOL;
+    if (ok) {
+        for (int c = lane; c < NCOL; c += G) {
+            Real *x = tl + IA::COL + c * ND;
+            const bool vel = c == 1 || c == C_TOT;
+            Real lam[NJ];
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) lam[j] = 0;
+            if (point) {
+                /* lambda = -S^-1 (J A + beta), A += Y lambda */
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) {
+                    Real s = vel ? tl[IA::BETA + j] : Real(0);
+                    for (int d = 0; d < ND; ++d) s += tl[IA::JR + j * ND + d] * x[d];
+                    lam[j] = -s;
+                }
+#pragma unroll
+                for (int k = 0; k < NJ; ++k) {
+#pragma unroll
+                    for (int j = 0; j < k; ++j) lam[k] -= tl[IA::SS + k * NJ + j] * lam[j];
+                    lam[k] *= tl[IA::SD + k];
+                }
+#pragma unroll
+                for (int k = NJ - 1; k >= 0; --k) {
+#pragma unroll
+                    for (int i = k + 1; i < NJ; ++i) lam[k] -= tl[IA::SS + i * NJ + k] * lam[i];
+                    lam[k] *= tl[IA::SD + k];
+                }
+                for (int d = 0; d < ND; ++d) {
+                    Real s = x[d];
+#pragma unroll
+                    for (int j = 0; j < NJ; ++j) s += tl[IA::COL + (NCOL + j) * ND + d] * lam[j];
+                    x[d] = s;
+                }
+            }
+            if (a.reaction) {
+#pragma unroll
+                for (int f = 0; f < NF; ++f)
+#pragma unroll
+                    for (int r = 0; r < 3; ++r)
+                        GAT(a.reaction, ((crow + c) * NF + f) * 3 + r, crows * NF * 3) = r < NR ? lam[f * NR + (r < NR ? r : 0)] : Real(0);
+            }
+            if (a.com_accel) {
+                const Real im = Real(1) / tl[IA::CB + 3];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    Real s = vel ? tl[IA::CB + i] * im : Real(0);
+                    for (int d = 0; d < ND; ++d) s += tl[IA::JC + i * ND + d] * x[d];
+                    GAT(a.com_accel, (crow + c) * 3 + i, crows * 3) = s;
+                }
+            }
+        }
+    }
+    wave_sync();
+    if (a.accel) {
+        for (int e = lane; e < NCOL * ND; e += G)
+            GAT(a.accel, crow * ND + e, crows * ND) = ok ? tl[IA::COL + e] : Real(0);
+    }
+    if (!ok) {
+        if (a.reaction)
+            for (int e = lane; e < NCOL * NF * 3; e += G) GAT(a.reaction, crow * NF * 3 + e, crows * NF * 3) = Real(0);
+        if (a.com_accel)
+            for (int e = lane; e < NCOL * 3; e += G) GAT(a.com_accel, crow * 3 + e, crows * 3) = Real(0);
+    }
+    if (lane < NF) {
+        const bool held = ok && tl[IA::PF + 4 * lane + 3] > 0;
+        if (a.cactive_out) GAT(a.cactive_out, (size_t)idx * NF + lane, (size_t)a.n * NF) = held ? 1 : 0;
+        if (a.cpoint_out) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+                GAT(a.cpoint_out, ((size_t)idx * NF + lane) * 3 + i, (size_t)a.n * NF * 3) =
+                    held ? tl[IA::PF + 4 * lane + i] + (i == 0 ? x0 : Real(0)) : Real(0);
+        }
+    }
+    if (lane == 0 && a.status) a.status[idx] = ok ? 0 : -2;
+}
+
 /* ---------------------------------------------------------------- kernel
  * Launch arguments of one env segment (one handle).  mode 0: env step
  * (optionally with in-kernel auto-reset); mode 1: reset the listed envs.
@@ -5693,6 +6215,18 @@ struct JrCall {   /* bioim_joint_reaction's arguments (untyped), for Ops::jr_lau
     void *reaction, *point, *tau_joint, *muscle_wrench;
 };
 
+struct IaCall {   /* bioim_induced_accel's arguments (untyped), for Ops::ia_launch */
+    int n;
+    const void *q, *u, *ft, *tau_act, *ext;
+    int kind;
+    const uint8_t *cactive;
+    const void *cpoint;
+    double force_threshold;
+    void *accel, *com_accel, *reaction, *cpoint_out;
+    uint8_t *cactive_out;
+    int32_t *status;
+};
+
 struct Ops {
     const char *topo;   /* the topology struct's name (fused-pair lookup) */
     int lanes;
@@ -5710,6 +6244,8 @@ struct Ops {
     void (*ik_launch)(bioim_handle_t *, const IkCall &);
     /* bioim_joint_reaction's launcher (every topology, both precisions); < 0: the fp64 image's upload failed */
     int (*jr_launch)(bioim_handle_t *, const JrCall &);
+    /* bioim_induced_accel's launcher (every topology); null for an fp32 handle (fp64 kernels only) */
+    void (*ia_launch)(bioim_handle_t *, const IaCall &);
     /* the fused rollout kernel's launcher; null where that instantiation is
      * left out (bioim_rollout then loops over `launch`) */
     void (*rollout)(bioim_handle_t *, const RolloutCall &);
@@ -6070,6 +6606,25 @@ template <class T, typename IO> int jr_launch_impl(bioim_handle_t *h, const JrCa
     return 0;
 }
 
+/* its own LDS size (IaLay: the env regions plus the private tails) and states per workgroup */
+template <class T> void ia_launch_impl(bioim_handle_t *h, const IaCall &c) {
+    using Real = double;
+    constexpr int EPB = IaLay<T, Real>::EPB;
+    IaArgs<T, Real> a;
+    a.Mg = reinterpret_cast<const DModel<Real> *>(h->model);
+    a.Sg = reinterpret_cast<const SModel<T, Real> *>(h->smodel);
+    a.n = c.n; a.kind = c.kind; a.thr = c.force_threshold;
+    a.q = reinterpret_cast<const Real *>(c.q); a.u = reinterpret_cast<const Real *>(c.u);
+    a.ft = reinterpret_cast<const Real *>(c.ft); a.tau_act = reinterpret_cast<const Real *>(c.tau_act);
+    a.ext = reinterpret_cast<const Real *>(c.ext); a.cpoint = reinterpret_cast<const Real *>(c.cpoint);
+    a.cactive = c.cactive;
+    a.accel = reinterpret_cast<Real *>(c.accel); a.com_accel = reinterpret_cast<Real *>(c.com_accel);
+    a.reaction = reinterpret_cast<Real *>(c.reaction); a.cpoint_out = reinterpret_cast<Real *>(c.cpoint_out);
+    a.cactive_out = c.cactive_out; a.status = c.status;
+    constexpr size_t lds = IaLay<T, Real>::lds_bytes;
+    hipLaunchKernelGGL((ia_kernel<T, Real>), dim3((c.n + EPB - 1) / EPB), dim3(EPB * T::G), lds, h->stream, a);
+}
+
 template <class T, typename Real> int upload_smodel(bioim_handle_t *h) {
     static_assert(lds_bytes<T, Real, true>() <= 163840, "LDS image + env regions exceed 160 KiB");
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&env_kernel<T, Real, false, false>),
@@ -6103,6 +6658,9 @@ template <class T, typename Real> int upload_smodel(bioim_handle_t *h) {
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, double, false>()));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&jr_kernel<T, Real>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, double, false>()));
+    if constexpr (std::is_same<Real, double>::value)
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&ia_kernel<T, double>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)IaLay<T, double>::lds_bytes));
     constexpr size_t B = smodel_bytes<T, Real>();
     std::vector<unsigned char> img(B, 0);
     build_smodel<T, Real>(h->pack, *reinterpret_cast<SModel<T, Real> *>(img.data()));
@@ -6121,6 +6679,7 @@ template <class T> bool pick(const bioim_modelpack_t &p, int precision, Ops &ops
     ops.ma_launch = nullptr;
     ops.so_launch = nullptr;
     ops.ik_launch = precision == 64 ? &ik_launch_impl<T> : nullptr;
+    ops.ia_launch = precision == 64 ? &ia_launch_impl<T> : nullptr;
     if (precision == 64) ops.jr_launch = &jr_launch_impl<T, double>;
     else ops.jr_launch = &jr_launch_impl<T, float>;
     if constexpr (T::NM > 0) {
@@ -6898,6 +7457,32 @@ int bioim_joint_reaction(bioim_handle_t *h, int n, const void *q, const void *u,
     HIPCHK(hipSetDevice(h->device));
     const JrCall c{n, q, u, qdd, ft, ext, flags, frame, reaction, point, tau_joint, muscle_wrench};
     if (const int rc = h->ops.jr_launch(h, c)) return rc;
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int bioim_induced_accel(bioim_handle_t *h, int n, const void *q, const void *u, const void *ft, const void *tau_act,
+                        const void *ext, int kind, const uint8_t *cactive, const void *cpoint, double force_threshold,
+                        void *accel, void *com_accel, void *reaction, void *cpoint_out, uint8_t *cactive_out,
+                        int32_t *status) {
+    if (!h) return fail(BIOIM_E_ARG, "bioim_induced_accel: null handle");
+    if (n < 0) return fail(BIOIM_E_ARG, "bioim_induced_accel: negative n");
+    if (n > 0 && !q) return fail(BIOIM_E_ARG, "bioim_induced_accel: null q");
+    if (ft && h->nmuscle <= 0) return fail(BIOIM_E_ARG, "bioim_induced_accel: ft on a model without muscles");
+    if (kind < BIOIM_IA_FORCE || kind > BIOIM_IA_POINT)
+        return fail(BIOIM_E_ARG, "bioim_induced_accel: kind must be BIOIM_IA_FORCE or BIOIM_IA_POINT");
+    if ((cactive == nullptr) != (cpoint == nullptr))
+        return fail(BIOIM_E_ARG, "bioim_induced_accel: cactive and cpoint go together");
+    if (!std::isfinite(force_threshold) || force_threshold < 0)
+        return fail(BIOIM_E_ARG, "bioim_induced_accel: force_threshold must be finite and >= 0");
+    if (!accel && !com_accel && !reaction && !cpoint_out && !cactive_out && !status)
+        return fail(BIOIM_E_ARG, "bioim_induced_accel: no output requested");
+    if (h->precision != 64 || !h->ops.ia_launch) return fail(BIOIM_E_ARG, "bioim_induced_accel: fp64 handles only");
+    if (n == 0) return 0;
+    HIPCHK(hipSetDevice(h->device));
+    const IaCall c{n, q, u, ft, tau_act, ext, kind, cactive, cpoint, force_threshold,
+                   accel, com_accel, reaction, cpoint_out, cactive_out, status};
+    h->ops.ia_launch(h, c);
     HIPCHK(hipGetLastError());
     return 0;
 }

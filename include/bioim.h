@@ -400,6 +400,88 @@ int bioim_joint_reaction(bioim_handle_t *h, int n, const void *q, const void *u 
         void *point /* [n][ncbody][3]: c_b in the ground frame */,
         void *tau_joint /* [n][ndof] */,
         void *muscle_wrench /* [n][ncbody][6]: the muscles' net wrench on body k alone (not the subtree), ground frame, about the ground origin */);
+/* Induced accelerations (OpenSim's InducedAccelerations analysis) at n
+ * arbitrary states, not the handle's envs: the env state and the realize cache
+ * are neither read nor written.  Per state: how much of each coordinate's
+ * acceleration, of the mass centre's acceleration and of each foot's ground
+ * reaction is due to gravity, to the velocity terms, and to each single force.
+ * fp64 handles only: every column goes through M^-1, and POINT mode through a
+ * Schur complement J M^-1 J^T on a floating base, whose conditioning leaves an
+ * fp32 result no digits worth reporting.  All pointers are device pointers
+ * (doubles unless noted), dof order as for bioim_id_eval.
+ *
+ * Contributors.  NC = 6 + ncforce + nmuscle columns, in this fixed order, each
+ * with its generalized force Q_c:
+ *   0            gravity     g(q) (BIOIM_ID_GRAVITY);
+ *   1            velocity    -c(q, u) (BIOIM_ID_CORIOLIS, negated);
+ *   2 ..         one per Hunt-Crossley force f (the feet): J^T of the force's
+ *                explicit sphere forces at (q, u), which is what bioim_id_eval
+ *                applies.  In POINT mode it is exactly 0 for a constrained foot;
+ *   then         limits      the coordinate limit forces;
+ *   then         actuators   tau_act [n][ndof], given by the caller (coordinate
+ *                actuators, PD torques, reserves).  NULL: zeros;
+ *   then         external    projection of ext [n][ncbody][6], with
+ *                bioim_joint_reaction's convention (fx fy fz mx my mz, ground
+ *                frame, moment about the ground origin).  NULL: zeros;
+ *   then         one per muscle m: -Ft_m dL_m/dq, the full generalized force
+ *                including a moving point's own-coordinate term.  The muscle
+ *                columns sum to bioim_muscle_eval's tau.  ft [n][nmuscle] NULL:
+ *                zeros, bit for bit;
+ *   last         total       the sum of all Q_c.
+ * Modes (kind).
+ *   BIOIM_IA_FORCE = 0: contact is the applied Hunt-Crossley force.
+ *     A_c = M^-1 Q_c.  The total column is then the model's forward-dynamics
+ *     acceleration.
+ *   BIOIM_IA_POINT = 1: OpenSim's way.  Each foot in contact is held by a point
+ *     constraint, and each contributor's share of the ground reaction is solved
+ *     for:
+ *         M A_c - sum_f J_f^T lambda_{c,f} = Q_c,
+ *         J_f A_c + [c is velocity or total] beta_f = 0  for every constrained f.
+ *     J_f is the station Jacobian (Omega_d x P_f + V_d) of the body-fixed point
+ *     coincident with P_f.  The body is the composite body that carries force
+ *     f's spheres.  beta_f is that point's acceleration along q(t) = q + u t,
+ *     that is, at q'' = 0.  Rows per constrained foot: 3 on spatial topologies,
+ *     2 (x, y) on planar ones.  The planar z row is identically zero, and the
+ *     planar reaction z is exactly 0.  The total column here is the
+ *     constrained model's acceleration, not forward dynamics.
+ * Which feet are constrained, and where.  The caller gives both
+ * cactive [n][ncforce] (uint8) and cpoint [n][ncforce][3] (ground frame), or
+ * neither.  With neither, the model decides: foot f is constrained when the
+ * summed normal force of its active spheres exceeds force_threshold (finite,
+ * >= 0), and P_f is then sum_s fn_s P_s / sum_s fn_s over that foot's active
+ * spheres, with the contact point P_s and normal force fn_s of the model's
+ * Hunt-Crossley contact.  cactive and cpoint are ignored in FORCE mode.
+ * Outputs (any may be NULL, not all):
+ *   accel       [n][NC][ndof]        A_c;
+ *   com_accel   [n][NC][3]           J_com A_c, plus d^2/dt^2 com(q + u t) on
+ *                                    the velocity and total columns;
+ *   reaction    [n][NC][ncforce][3]  lambda_{c,f}.  Zeros in FORCE mode and for
+ *                                    unconstrained feet;
+ *   cpoint_out  [n][ncforce][3], cactive_out [n][ncforce] (uint8): what was
+ *                                    used (zeros for a foot not constrained);
+ *   status      [n] int32            0 ok; -2 for a pivot <= 0 or a NaN that
+ *                                    came in (from M or from the Schur
+ *                                    complement S = J M^-1 J^T, or through u,
+ *                                    ft, tau_act, ext).  The outputs are then
+ *                                    zeros.
+ * u NULL: zeros.  A state's result does not depend on n or on the other
+ * states, and a repeated call repeats it bit for bit (every sum has a fixed
+ * order).  BIOIM_E_ARG, before any device call and in this order, for: a null
+ * handle, n < 0, null q with n > 0, ft on a model without muscles, kind
+ * outside 0..1, exactly one of cactive / cpoint, force_threshold not finite or
+ * < 0, every output NULL, an fp32 handle.  n == 0 returns BIOIM_OK without a
+ * launch.  Asynchronous on the handle's stream; synchronizes nothing.  No
+ * reference counterpart (the reference ships no induced-acceleration
+ * analysis). */
+enum { BIOIM_IA_FORCE = 0, BIOIM_IA_POINT = 1 };   /* kind */
+int bioim_induced_accel(bioim_handle_t *h, int n, const void *q, const void *u /* NULL: 0 */,
+        const void *ft /* [n][nmuscle] tendon forces, NULL: none */,
+        const void *tau_act /* [n][ndof], NULL: none */,
+        const void *ext /* [n][ncbody][6] fx fy fz mx my mz on each body, ground frame, moment about the ground origin; NULL: none */,
+        int kind, const uint8_t *cactive /* [n][ncforce] */, const void *cpoint /* [n][ncforce][3], ground frame */,
+        double force_threshold,
+        void *accel /* [n][NC][ndof] */, void *com_accel /* [n][NC][3] */, void *reaction /* [n][NC][ncforce][3] */,
+        void *cpoint_out /* [n][ncforce][3] */, uint8_t *cactive_out /* [n][ncforce] */, int32_t *status /* [n] */);
 /* OsimModel calls on single envs (the reference's physics facade,
  * opensim_wrapper.py:92-332), for callers that drive the model directly
  * (tests/example_position_control.py:203-223; the env methods
