@@ -30,11 +30,12 @@ pack's composite-body order.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
+from ._analysis import Analysis, check_rows, check_want, ptr as p
+
+NAME = 'induced accelerations'
 
 KEYS = ('accel', 'com_accel', 'reaction', 'cpoint', 'cactive', 'status')
 DEFAULT_WANT = ('accel',)
@@ -70,14 +71,7 @@ def check_args(ndof, nmuscle, ncbody, ncforce, q, u=None, ft=None, tau_act=None,
     shapes, real dtypes, the keys of ``want``, ``kind``, ``cactive`` and
     ``cpoint`` together or not at all, a finite ``force_threshold`` >= 0, no
     ``ft`` on a model without muscles.  Returns (n, the requested keys)."""
-    if isinstance(want, str):
-        want = (want,)
-    want = tuple(want)
-    if not want:
-        raise ValueError('induced accelerations: nothing requested (want is empty)')
-    for k in want:
-        if k not in KEYS:
-            raise ValueError(f'induced accelerations: unknown key {k!r}; choose from {KEYS}')
+    want = check_want(NAME, want, KEYS)
     if kind not in KINDS:
         raise ValueError(f'induced accelerations: unknown kind {kind!r}; choose from {tuple(KINDS)}')
     if q is None:
@@ -92,32 +86,9 @@ def check_args(ndof, nmuscle, ncbody, ncforce, q, u=None, ft=None, tau_act=None,
         raise ValueError(f'induced accelerations: force_threshold must be a number, got {force_threshold!r}') from None
     if not np.isfinite(thr) or thr < 0:
         raise ValueError(f'induced accelerations: force_threshold must be finite and >= 0, got {force_threshold!r}')
-
-    def dkind(x):
-        dt = x.dtype
-        if isinstance(dt, np.dtype):
-            return dt.kind
-        if dt.is_floating_point:      # a torch dtype
-            return 'f'
-        return 'c' if dt.is_complex else ('b' if 'bool' in str(dt) else 'i')
-
-    def rows(x, what, tail, kinds='fiu'):
-        if not hasattr(x, 'dtype') or not hasattr(x, 'shape'):
-            x = np.asarray(x)
-        if dkind(x) not in kinds:
-            raise ValueError(f'induced accelerations: {what} must hold real numbers, got dtype {x.dtype}')
-        s = tuple(x.shape)
-        if len(s) != 1 + len(tail) or s[1:] != tail:
-            raise ValueError(f'induced accelerations: {what} must have shape (n, {", ".join(map(str, tail))}), got {s}')
-        return s[0]
-    n = rows(q, 'q', (ndof,))
-    for x, what, tail, kinds in ((u, 'u', (ndof,), 'fiu'), (ft, 'ft', (nmuscle,), 'fiu'),
-                                 (tau_act, 'tau_act', (ndof,), 'fiu'), (ext, 'ext', (ncbody, 6), 'fiu'),
-                                 (cactive, 'cactive', (ncforce,), 'fiub'), (cpoint, 'cpoint', (ncforce, 3), 'fiu')):
-        if x is not None:
-            nx = rows(x, what, tail, kinds)
-            if nx != n:
-                raise ValueError(f'induced accelerations: {what} has {nx} rows, q has {n}')
+    n = check_rows(NAME, (q, 'q', (ndof,)),
+                   ((u, 'u', (ndof,)), (ft, 'ft', (nmuscle,)), (tau_act, 'tau_act', (ndof,)), (ext, 'ext', (ncbody, 6)),
+                    (cactive, 'cactive', (ncforce,), 'fiub'), (cpoint, 'cpoint', (ncforce, 3))))
     return n, want
 
 
@@ -134,7 +105,6 @@ def launch(env, q, u, ft, tau_act, ext, kind, cactive, cpoint, force_threshold, 
     pk = env.pack
     n, nd, nf = q.shape[0], pk.ndof, pk.ncforce
     nc = 6 + nf + pk.nmuscle
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
     shapes = dict(accel=((n, nc, nd), env.dtype), com_accel=((n, nc, 3), env.dtype),
                   reaction=((n, nc, nf, 3), env.dtype), cpoint=((n, nf, 3), env.dtype),
                   cactive=((n, nf), torch.uint8), status=((n,), torch.int32))
@@ -198,15 +168,13 @@ def dof_names(pack, names):
     return [cn[c] for d in range(pack.ndof) for c in range(pack.ncoord) if pack.coord[c].dof == d]
 
 
-class InducedAccelerations:
+class InducedAccelerations(Analysis):
     def __init__(self, env_id: str, device: int = 0):
         from .obslayout import load_names
-        from .vector_env import VectorEnv
-        self._env = VectorEnv(env_id, 1, device=device, precision=64)
+        super().__init__(env_id, device, 64)
         pk = self._env.pack
         names = load_names(env_id)
         self.ndof, self.ncbody, self.nmuscle, self.ncforce = pk.ndof, pk.ncbody, pk.nmuscle, pk.ncforce
-        self.device, self.dtype = self._env.device, self._env.dtype
         self.contributors = contributor_names(pk, names)
         self.coords = dof_names(pk, names)
 
@@ -225,13 +193,7 @@ class InducedAccelerations:
         import torch
         n, want = check_args(self.ndof, self.nmuscle, self.ncbody, self.ncforce, q, u, ft, tau_act, ext, kind,
                              cactive, cpoint, force_threshold, want)
-
-        def dev(x, dtype=None):
-            if x is None:
-                return None
-            if isinstance(x, np.ndarray) and not x.flags.writeable:
-                x = x.copy()      # torch does not wrap read-only arrays
-            return torch.as_tensor(x).to(device=self.device, dtype=dtype or self.dtype).contiguous()
+        dev = self._dev
         ca = None
         if cactive is not None:
             ca = (dev(cactive, torch.float64) != 0).to(torch.uint8).contiguous()
@@ -242,6 +204,3 @@ class InducedAccelerations:
 
     def write_sto(self, path, time, out, quantity):
         write_sto(path, time, out, quantity, contributors=self.contributors, coords=self.coords)
-
-    def close(self):
-        self._env.close()

@@ -25,23 +25,20 @@ freedom: their input entries are ignored and their outputs are 0.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
+from ._analysis import Analysis, ptr as p
 
 GRAVITY, CORIOLIS, MULT_M, MULT_MINV, RESIDUAL, TOTAL = range(6)
 
 
-class InverseDynamics:
+class InverseDynamics(Analysis):
     def __init__(self, env_id: str, device: int = 0, precision: int = 64):
-        from .vector_env import VectorEnv
-        self._env = VectorEnv(env_id, 1, device=device, precision=precision)
+        super().__init__(env_id, device, precision)
         pk = self._env.pack
         self.ndof, self.ncoord = pk.ndof, pk.ncoord
         self.dof = np.array([pk.coord[c].dof for c in range(pk.ncoord)])
-        self.device, self.dtype = self._env.device, self._env.dtype
         self._state = None
 
     # ------------------------------------------------------------ batched
@@ -50,16 +47,10 @@ class InverseDynamics:
         q, u, v: [n][ndof] tensors (any device/dtype; moved to the env's).
         Returns a [n][ndof] tensor on the env's device."""
         import torch
-
-        def dev(x):
-            if x is None:
-                return None
-            return torch.as_tensor(x).to(device=self.device, dtype=self.dtype).contiguous()
-        q, u, v = dev(q), dev(u), dev(v)
+        q, u, v = self._dev(q), self._dev(u), self._dev(v)
         n = q.shape[0]
         assert q.shape == (n, self.ndof)
         out = torch.empty((n, self.ndof), device=self.device, dtype=self.dtype)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
         _lib.check(self._env._L.bioim_id_eval(self._env._h, int(op), n, p(q), p(u), p(v), p(out)))
         return out
 
@@ -100,6 +91,3 @@ class InverseDynamics:
 
     def multiplyByMInv(self, t, q, tau):
         return self._coords(self.eval(MULT_MINV, self._dofs(q), v=self._dofs(tau)))
-
-    def close(self):
-        self._env.close()

@@ -27,40 +27,19 @@ fp64 only.  There is no CPU path.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import numpy as np
 
 from . import _lib
+from ._analysis import Analysis, check_rows, check_shape, check_want, ptr as p
+
+NAME = 'inverse kinematics'
 
 KEYS = ('q', 'markers', 'err', 'jacobian', 'status')
 DEFAULT_WANT = ('q', 'status')
 MAX_MARKERS = 64      # BIOIM_IK_MAX_MARKERS (include/bioim.h)
 ERR_COLUMNS = ('marker_rms', 'marker_max')
-
-
-def _kind(x):
-    dt = x.dtype
-    if isinstance(dt, np.dtype):
-        return dt.kind
-    if dt.is_floating_point:      # a torch dtype
-        return 'f'
-    return 'c' if dt.is_complex else ('b' if 'bool' in str(dt) else 'i')
-
-
-def _shape(x, what, shape_ok, want_shape):
-    if not hasattr(x, 'dtype') or not hasattr(x, 'shape'):
-        try:
-            x = np.asarray(x)
-        except (TypeError, ValueError):
-            raise ValueError(f'inverse kinematics: {what} must hold real numbers') from None
-    if _kind(x) not in 'fiu':
-        raise ValueError(f'inverse kinematics: {what} must hold real numbers, got dtype {x.dtype}')
-    s = tuple(x.shape)
-    if not shape_ok(s):
-        raise ValueError(f'inverse kinematics: {what} must have shape {want_shape}, got {s}')
-    return s
 
 
 def _host(x):
@@ -75,27 +54,15 @@ def check_args(ndof, nm, x_exp, weights=None, q0=None, coord_weight=None, q_targ
     non-negative and given together with ``q_target``, ``tol`` finite and
     non-negative, ``max_iter`` a non-negative integer, the keys of ``want``.
     Returns (n, the requested keys as a tuple)."""
-    if isinstance(want, str):
-        want = (want,)
-    want = tuple(want)
-    if not want:
-        raise ValueError('inverse kinematics: nothing requested (want is empty)')
-    for k in want:
-        if k not in KEYS:
-            raise ValueError(f'inverse kinematics: unknown key {k!r}; choose from {KEYS}')
+    want = check_want(NAME, want, KEYS)
     if x_exp is None:
         raise ValueError('inverse kinematics: x_exp is required')
-    n = _shape(x_exp, 'x_exp', lambda s: len(s) == 3 and s[1:] == (nm, 3), f'(n, {nm}, 3)')[0]
-    for x, what in ((q0, 'q0'), (q_target, 'q_target')):
-        if x is not None:
-            nx = _shape(x, what, lambda s: len(s) == 2 and s[1] == ndof, f'(n, {ndof})')[0]
-            if nx != n:
-                raise ValueError(f'inverse kinematics: {what} has {nx} rows, x_exp has {n} frames')
+    n = check_rows(NAME, (x_exp, 'x_exp', (nm, 3)), ((q0, 'q0', (ndof,)), (q_target, 'q_target', (ndof,))), ' frames')
     if (coord_weight is None) != (q_target is None):
         raise ValueError('inverse kinematics: coord_weight and q_target go together (both or neither)')
     for x, what, m in ((weights, 'weights', nm), (coord_weight, 'coord_weight', ndof)):
         if x is not None:
-            _shape(x, what, lambda s, m=m: s == (m,), f'({m},)')
+            check_shape(NAME, x, what, (m,), batched=False)
             v = _host(x)
             if not np.isfinite(v).all() or (v < 0).any():
                 raise ValueError(f'inverse kinematics: {what} must be finite and non-negative')
@@ -158,7 +125,7 @@ def map_markers(pack, body_names, markers, marker_set=None):
     return names, np.array(cb, dtype=np.int32), np.array(loc, dtype=np.float64)
 
 
-class InverseKinematics:
+class InverseKinematics(Analysis):
     def __init__(self, env_id: str, markers, marker_set=None, device: int = 0):
         from .obslayout import load_names
         from .registry import load_pack
@@ -167,12 +134,10 @@ class InverseKinematics:
         self.marker_names, cb, loc = map_markers(pk, names['bodies'], markers, marker_set)   # before any device call
         if (cb < 0).any() or (cb >= pk.ncbody).any():
             raise ValueError('inverse kinematics: a marker body lies outside the model')
-        from .vector_env import VectorEnv
         import torch
-        self._env = VectorEnv(env_id, 1, device=device, precision=64)
+        super().__init__(env_id, device, 64)
         pk = self._env.pack
         self.ndof, self.ncoord, self.nm = pk.ndof, pk.ncoord, len(cb)
-        self.device, self.dtype = self._env.device, self._env.dtype
         self.coordinate_names = list(names['coords'])
         self.dof = np.array([pk.coord[c].dof for c in range(pk.ncoord)])
         self.default_coords = np.array([pk.coord[c].default_value for c in range(pk.ncoord)])
@@ -188,19 +153,10 @@ class InverseKinematics:
         self._loc = torch.as_tensor(loc, device=self.device).contiguous()
         self._ones = torch.ones(self.nm, device=self.device, dtype=torch.float64)
 
-    def _dev(self, x):
-        import torch
-        if x is None:
-            return None
-        if isinstance(x, np.ndarray) and not x.flags.writeable:
-            x = x.copy()      # torch does not wrap read-only arrays
-        return torch.as_tensor(x).to(device=self.device, dtype=torch.float64).contiguous()
-
     def _launch(self, n, x_exp, w, q0, cw, qt, tol, max_iter, want):
         import torch
         env, nd, nm = self._env, self.ndof, self.nm
         new = lambda *s: torch.empty(s, device=self.device, dtype=torch.float64)  # noqa: E731
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
         bufs = dict(q=new(n, nd), markers=None, err=None, jacobian=None, status=None)
         if 'markers' in want:
             bufs['markers'] = new(n, nm, 3)
@@ -257,7 +213,7 @@ class InverseKinematics:
         """The forward marker kinematics at q [n][ndof] (the ``max_iter=0``
         call): ``markers`` and ``jacobian``, and with ``x_exp`` also ``err``."""
         import torch
-        _shape(q, 'q', lambda s: len(s) == 2 and s[1] == self.ndof, f'(n, {self.ndof})')
+        check_shape(NAME, q, 'q', (self.ndof,))
         q = self._dev(q)
         n = q.shape[0]
         if x_exp is None:
@@ -303,6 +259,3 @@ class InverseKinematics:
         ``refmotion.synthesize_reference`` takes."""
         from .storage import write_sto
         write_sto(path, ['time'] + self.coordinate_names, np.column_stack([time, q_coords]), name='Coordinates')
-
-    def close(self):
-        self._env.close()

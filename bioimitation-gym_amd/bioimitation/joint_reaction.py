@@ -32,11 +32,12 @@ pack's composite-body order.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
+from ._analysis import Analysis, check_rows, check_want, ptr as p
+
+NAME = 'joint reaction'
 
 KEYS = ('reaction', 'point', 'tau_joint', 'muscle_wrench')
 DEFAULT_WANT = ('reaction',)
@@ -131,43 +132,14 @@ def check_args(ndof, nmuscle, ncbody, q, u=None, qdd=None, ft=None, ext=None, fr
     ``[n][ndof]`` / ``[n][nmuscle]`` / ``[n][ncbody][6]``, real dtypes, the keys
     of ``want``, ``frame`` and ``on``, no ``ft`` on a model without muscles.
     Returns (n, the requested keys as a tuple)."""
-    if isinstance(want, str):
-        want = (want,)
-    want = tuple(want)
-    if not want:
-        raise ValueError('joint reaction: nothing requested (want is empty)')
-    for k in want:
-        if k not in KEYS:
-            raise ValueError(f'joint reaction: unknown key {k!r}; choose from {KEYS}')
+    want = check_want(NAME, want, KEYS)
     check_frame(frame, on)
     if q is None:
         raise ValueError('joint reaction: q is required')
     if ft is not None and nmuscle == 0:
         raise ValueError('joint reaction: ft given, but the model has no muscles')
-
-    def kind(x):
-        dt = x.dtype
-        if isinstance(dt, np.dtype):
-            return dt.kind
-        if dt.is_floating_point:      # a torch dtype
-            return 'f'
-        return 'c' if dt.is_complex else ('b' if 'bool' in str(dt) else 'i')
-
-    def rows(x, what, tail):
-        if not hasattr(x, 'dtype') or not hasattr(x, 'shape'):
-            x = np.asarray(x)
-        if kind(x) not in 'fiu':
-            raise ValueError(f'joint reaction: {what} must hold real numbers, got dtype {x.dtype}')
-        s = tuple(x.shape)
-        if len(s) != 1 + len(tail) or s[1:] != tail:
-            raise ValueError(f'joint reaction: {what} must have shape (n, {", ".join(map(str, tail))}), got {s}')
-        return s[0]
-    n = rows(q, 'q', (ndof,))
-    for x, what, tail in ((u, 'u', (ndof,)), (qdd, 'qdd', (ndof,)), (ft, 'ft', (nmuscle,)), (ext, 'ext', (ncbody, 6))):
-        if x is not None:
-            nx = rows(x, what, tail)
-            if nx != n:
-                raise ValueError(f'joint reaction: {what} has {nx} rows, q has {n}')
+    n = check_rows(NAME, (q, 'q', (ndof,)),
+                   ((u, 'u', (ndof,)), (qdd, 'qdd', (ndof,)), (ft, 'ft', (nmuscle,)), (ext, 'ext', (ncbody, 6))))
     return n, want
 
 
@@ -178,7 +150,6 @@ def launch(env, q, u, qdd, ft, ext, contact, frame, on, want):
     import torch
     n, nd, nb = q.shape[0], env.pack.ndof, env.pack.ncbody
     new = lambda *s: torch.empty(s, device=env.device, dtype=env.dtype)  # noqa: E731
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
     shapes = dict(reaction=(n, nb, 6), point=(n, nb, 3), tau_joint=(n, nd), muscle_wrench=(n, nb, 6))
     bufs = {k: (new(*shapes[k]) if k in want else None) for k in KEYS}
     if n:      # (empty tensors have null pointers, which the library reads as outputs not requested)
@@ -217,14 +188,12 @@ def write_sto(path, time, out, table=None, frame=None, on=None):
     storage.write_sto(path, ['time'] + table.columns(frame, on), data, name='JointReaction')
 
 
-class JointReaction:
+class JointReaction(Analysis):
     def __init__(self, env_id: str, device: int = 0, precision: int = 64):
-        from .vector_env import VectorEnv
         self.table = JointTable(env_id)
-        self._env = VectorEnv(env_id, 1, device=device, precision=precision)
+        super().__init__(env_id, device, precision)
         pk = self._env.pack
         self.ndof, self.ncbody, self.nmuscle = pk.ndof, pk.ncbody, pk.nmuscle
-        self.device, self.dtype = self._env.device, self._env.dtype
         self.joints = list(self.table.joints)          # one per composite body; inner joints have no row
         self.inner_joints = dict(self.table.inner)     # {name: why it has no row}
 
@@ -236,21 +205,11 @@ class JointReaction:
         """q, u, qdd: [n][ndof]; ft: [n][nmuscle]; ext: [n][ncbody][6] (tensors
         or arrays, any device / real dtype; moved to the env's).  Returns a
         dict of device tensors for the keys of ``want`` (``KEYS``)."""
-        import torch
         n, want = check_args(self.ndof, self.nmuscle, self.ncbody, q, u, qdd, ft, ext, frame, on, want)
-
-        def dev(x):
-            if x is None:
-                return None
-            if isinstance(x, np.ndarray) and not x.flags.writeable:
-                x = x.copy()      # torch does not wrap read-only arrays
-            return torch.as_tensor(x).to(device=self.device, dtype=self.dtype).contiguous()
+        dev = self._dev
         res = Result(launch(self._env, dev(q), dev(u), dev(qdd), dev(ft), dev(ext), contact, frame, on, want))
         res.table, res.frame, res.on = self.table, frame, on
         return res
 
     def write_sto(self, path, time, out):
         write_sto(path, time, out, table=self.table)
-
-    def close(self):
-        self._env.close()

@@ -22,11 +22,12 @@ order (``muscle_names``).
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
+from ._analysis import Analysis, check_rows, check_want, ptr as p
+
+NAME = 'muscle analysis'
 
 KEYS = ('length', 'speed', 'dldq', 'moment_arms', 'fiber', 'tau')
 FIBER_COLUMNS = ('fiber_length', 'fiber_velocity', 'tendon_force', 'fiber_force', 'active_fiber_force')
@@ -38,40 +39,11 @@ def check_args(ndof, nmuscle, q, u=None, act=None, lce=None, want=DEFAULT_WANT):
     """The argument checks of ``MuscleAnalysis.eval`` (no device needed):
     shapes ``[n][ndof]`` / ``[n][nmuscle]``, real dtypes, the keys of ``want``
     and the inputs they need.  Returns (n, the requested keys as a tuple)."""
-    if isinstance(want, str):
-        want = (want,)
-    want = tuple(want)
-    if not want:
-        raise ValueError('muscle analysis: nothing requested (want is empty)')
-    for k in want:
-        if k not in KEYS:
-            raise ValueError(f'muscle analysis: unknown key {k!r}; choose from {KEYS}')
+    want = check_want(NAME, want, KEYS)
     if q is None:
         raise ValueError('muscle analysis: q is required')
 
-    def kind(x):
-        dt = x.dtype
-        if isinstance(dt, np.dtype):
-            return dt.kind
-        if dt.is_floating_point:      # a torch dtype
-            return 'f'
-        return 'c' if dt.is_complex else ('b' if 'bool' in str(dt) else 'i')
-
-    def rows(x, what, cols):
-        if not hasattr(x, 'dtype') or not hasattr(x, 'shape'):
-            x = np.asarray(x)
-        if kind(x) not in 'fiu':
-            raise ValueError(f'muscle analysis: {what} must hold real numbers, got dtype {x.dtype}')
-        s = tuple(x.shape)
-        if len(s) != 2 or s[1] != cols:
-            raise ValueError(f'muscle analysis: {what} must have shape (n, {cols}), got {s}')
-        return s[0]
-    n = rows(q, 'q', ndof)
-    for x, what, cols in ((u, 'u', ndof), (act, 'act', nmuscle), (lce, 'lce', nmuscle)):
-        if x is not None:
-            nx = rows(x, what, cols)
-            if nx != n:
-                raise ValueError(f'muscle analysis: {what} has {nx} rows, q has {n}')
+    n = check_rows(NAME, (q, 'q', (ndof,)), ((u, 'u', (ndof,)), (act, 'act', (nmuscle,)), (lce, 'lce', (nmuscle,))))
     if act is None:
         for k in ('fiber', 'tau'):
             if k in want:
@@ -86,7 +58,6 @@ def launch(env, q, u, act, lce, want):
     import torch
     n, nd, nm = q.shape[0], env.pack.ndof, env.pack.nmuscle
     new = lambda *s: torch.empty(s, device=env.device, dtype=env.dtype)  # noqa: E731
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
     if nm == 0:   # a torque model: the library's own refusal (the output given is never written)
         _lib.check(env._L.bioim_muscle_eval(env._h, n, p(q), None, None, None, p(new(1)), None, None, None, None))
     bufs = dict(length=None, speed=None, dldq=None, fiber=None, tau=None)
@@ -110,14 +81,12 @@ def launch(env, q, u, act, lce, want):
     return out
 
 
-class MuscleAnalysis:
+class MuscleAnalysis(Analysis):
     def __init__(self, env_id: str, device: int = 0, precision: int = 64):
         from .obslayout import load_names
-        from .vector_env import VectorEnv
-        self._env = VectorEnv(env_id, 1, device=device, precision=precision)
+        super().__init__(env_id, device, precision)
         pk = self._env.pack
         self.ndof, self.ncoord, self.nmuscle = pk.ndof, pk.ncoord, pk.nmuscle
-        self.device, self.dtype = self._env.device, self._env.dtype
         names = load_names(env_id)
         self.muscle_names = list(names.get('muscles') or [])[:pk.nmuscle]
         self.coordinate_names = list(names['coords'])
@@ -127,16 +96,6 @@ class MuscleAnalysis:
         """q, u: [n][ndof]; act, lce: [n][nmuscle] (tensors or arrays, any
         device / real dtype; moved to the env's).  Returns a dict of device
         tensors for the keys of ``want`` (``KEYS``)."""
-        import torch
         n, want = check_args(self.ndof, self.nmuscle, q, u, act, lce, want)
-
-        def dev(x):
-            if x is None:
-                return None
-            if isinstance(x, np.ndarray) and not x.flags.writeable:
-                x = x.copy()      # torch does not wrap read-only arrays
-            return torch.as_tensor(x).to(device=self.device, dtype=self.dtype).contiguous()
+        dev = self._dev
         return launch(self._env, dev(q), dev(u), dev(act), dev(lce), want)
-
-    def close(self):
-        self._env.close()

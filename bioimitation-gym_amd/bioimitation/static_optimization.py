@@ -36,13 +36,15 @@ order (``muscle_names``).
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 
 import numpy as np
 
 from . import _lib
+from ._analysis import Analysis, check_rows, check_want, ptr as p, to_device
 from .inverse_dynamics import RESIDUAL
+
+NAME = 'static optimization'
 
 KEYS = ('act', 'residual', 'tau_muscle', 'capacity', 'status', 'tau')
 DEFAULT_WANT = ('act',)
@@ -56,42 +58,12 @@ def check_args(ndof, nmuscle, q, u=None, qdd=None, tau=None, reserve=1.0, lo=0.0
     (``inf`` allowed), finite bounds with lo < hi, the keys of ``want``.
     Returns (n, the requested keys as a tuple, the row weights λ as a float64
     array ``[ndof]``)."""
-    if isinstance(want, str):
-        want = (want,)
-    want = tuple(want)
-    if not want:
-        raise ValueError('static optimization: nothing requested (want is empty)')
-    for k in want:
-        if k not in KEYS:
-            raise ValueError(f'static optimization: unknown key {k!r}; choose from {KEYS}')
+    want = check_want(NAME, want, KEYS)
     if q is None:
         raise ValueError('static optimization: q is required')
     if (qdd is None) == (tau is None):
         raise ValueError('static optimization: give exactly one of qdd and tau')
-
-    def kind(x):
-        dt = x.dtype
-        if isinstance(dt, np.dtype):
-            return dt.kind
-        if dt.is_floating_point:      # a torch dtype
-            return 'f'
-        return 'c' if dt.is_complex else ('b' if 'bool' in str(dt) else 'i')
-
-    def rows(x, what):
-        if not hasattr(x, 'dtype') or not hasattr(x, 'shape'):
-            x = np.asarray(x)
-        if kind(x) not in 'fiu':
-            raise ValueError(f'static optimization: {what} must hold real numbers, got dtype {x.dtype}')
-        s = tuple(x.shape)
-        if len(s) != 2 or s[1] != ndof:
-            raise ValueError(f'static optimization: {what} must have shape (n, {ndof}), got {s}')
-        return s[0]
-    n = rows(q, 'q')
-    for x, what in ((u, 'u'), (qdd, 'qdd'), (tau, 'tau')):
-        if x is not None:
-            nx = rows(x, what)
-            if nx != n:
-                raise ValueError(f'static optimization: {what} has {nx} rows, q has {n}')
+    n = check_rows(NAME, (q, 'q', (ndof,)), ((u, 'u', (ndof,)), (qdd, 'qdd', (ndof,)), (tau, 'tau', (ndof,))))
     try:
         lo, hi = float(lo), float(hi)
     except (TypeError, ValueError):
@@ -122,7 +94,6 @@ def launch(env, q, u, tau, lam, lo, hi, passive, want):
     import torch
     n, nd, nm = q.shape[0], env.pack.ndof, env.pack.nmuscle
     new = lambda *s: torch.empty(s, device=env.device, dtype=torch.float64)  # noqa: E731
-    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
     bufs = dict(act=new(n, nm), residual=None, tau_muscle=None, capacity=None, status=None)
     if 'residual' in want:
         bufs['residual'] = new(n, nd)
@@ -141,14 +112,12 @@ def launch(env, q, u, tau, lam, lo, hi, passive, want):
     return {k: bufs[k] for k in want}
 
 
-class StaticOptimization:
+class StaticOptimization(Analysis):
     def __init__(self, env_id: str, device: int = 0):
         from .obslayout import load_names
-        from .vector_env import VectorEnv
-        self._env = VectorEnv(env_id, 1, device=device, precision=64)
+        super().__init__(env_id, device, 64)
         pk = self._env.pack
         self.ndof, self.ncoord, self.nmuscle = pk.ndof, pk.ncoord, pk.nmuscle
-        self.device, self.dtype = self._env.device, self._env.dtype
         names = load_names(env_id)
         self.muscle_names = list(names.get('muscles') or [])[:pk.nmuscle]
         self.coordinate_names = list(names['coords'])
@@ -164,22 +133,13 @@ class StaticOptimization:
         n, want, lam = check_args(self.ndof, self.nmuscle, q, u, qdd, tau, reserve, lo, hi, want)
         return solve_on(self._env, q, u, qdd, tau, lam, lo, hi, passive, want)
 
-    def close(self):
-        self._env.close()
-
 
 def solve_on(env, q, u, qdd, tau, lam, lo, hi, passive, want):
     """The checked arguments of ``solve`` moved to ``env``'s device, the
     inverse-dynamics launch where the target is given as accelerations, then
     ``launch``."""
     import torch
-
-    def dev(x):
-        if x is None:
-            return None
-        if isinstance(x, np.ndarray) and not x.flags.writeable:
-            x = x.copy()      # torch does not wrap read-only arrays
-        return torch.as_tensor(x).to(device=env.device, dtype=torch.float64).contiguous()
+    dev = lambda x: to_device(x, env.device, torch.float64)  # noqa: E731
     check_env(env)
     q, u, qdd, tau = dev(q), dev(u), dev(qdd), dev(tau)
     n = q.shape[0]
@@ -187,7 +147,6 @@ def solve_on(env, q, u, qdd, tau, lam, lo, hi, passive, want):
         tau = torch.empty_like(q)
         if n:
             uu = u if u is not None else torch.zeros_like(q)
-            p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
             env._bind_stream()
             _lib.check(env._L.bioim_id_eval(env._h, RESIDUAL, n, p(q), p(uu), p(qdd), p(tau)))
     lam_dev = None if (lam == 1.0).all() else dev(lam)

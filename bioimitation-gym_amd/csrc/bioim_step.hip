@@ -1842,6 +1842,27 @@ template <class T, typename Real> struct CacheIO {
     Real mus[MPA][3];  /* PREFETCH: this lane's muscles' root, dv/dl, clamp flag */
 };
 
+/* Which device functions take their branch-free forms (selects over plain
+ * locals, blended extrapolations, one basic block per muscle eval) in topology
+ * T's kernels.  IMP: a semi-implicit kernel; the analysis kernels take the
+ * semi-implicit step's switches (the default).
+ * BFK: all of them in the planar kernels, except the torque-model RK ones: an
+ * RK build of these forms put a lane-divergent copy of a live-in-all-lanes
+ * address into an AGPR in the Torque2D RK kernel and faulted;
+ * that kernel keeps the GPU-verified code (round 4: the same forms there again
+ * give 4 flagged copies in tools/hazard_gate.py), and the gate checks the others.
+ * BF3: per piece in the spatial semi-implicit kernels (BIOIM_BF3 bits:
+ * 1 function slots, 2 muscle paths, 4 contact, 8 limits, 16 fiber equilibrium,
+ * 32 phase-3 rows, 64 implicit terms without a branch on h, 128 muscle eval) */
+template <class T, bool IMP = true> struct BfSwitch {
+    static constexpr bool BFK = (T::PLANAR || BIOIM_BF_SPATIAL) && (IMP || T::NM > 0);
+    static constexpr bool BF3 = !T::PLANAR && (IMP || BIOIM_BF3_RK);
+    static constexpr bool FN = BFK || (BF3 && (BIOIM_BF3 & 1)), PATH = BFK || (BF3 && (BIOIM_BF3 & 2));
+    static constexpr bool CON = BFK || (BF3 && (BIOIM_BF3 & 4)), LIM = BFK || (BF3 && (BIOIM_BF3 & 8));
+    static constexpr bool EQ = BFK || (BF3 && (BIOIM_BF3 & 16)), ROW = BFK || (BF3 && (BIOIM_BF3 & 32));
+    static constexpr bool ME = BFK || (BF3 && (BIOIM_BF3 & 128));
+};
+
 template <class T, typename Real, bool PERT, bool BF_ROWS, bool IMP, bool CACHE = false>
 DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Real ud,
                   const Real (&act)[Lay<T, Real>::MPL], const Real (&lce)[Lay<T, Real>::MPL],
@@ -1854,23 +1875,7 @@ DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Rea
     /* the semi-implicit planar kernels: the implicit contact / limit terms
      * without a branch on h (the spatial kernels keep it: register budget) */
     constexpr bool IMP_BF = IMP && (T::PLANAR || BIOIM_BF_SPATIAL || ((BIOIM_BF3 & 64) && !PERT));
-    /* the branch-free forms (selects over plain locals, blended
-     * extrapolations, one basic block per muscle eval) in the planar
-     * kernels, except the torque-model RK ones: an RK build of these forms
-     * put a lane-divergent copy of a live-in-all-lanes address into an AGPR
-     * in the Torque2D RK kernel and faulted; that kernel
-     * keeps the GPU-verified code (round 4: the same forms there again give 4
-     * flagged copies in tools/hazard_gate.py), and the gate checks the others */
-    constexpr bool BFK = (T::PLANAR || BIOIM_BF_SPATIAL) && (IMP || T::NM > 0);
-    /* per-piece switches of the branch-free forms in the spatial semi-implicit
-     * kernels (BIOIM_BF3 bits: 1 function slots, 2 muscle paths, 4 contact,
-     * 8 limits, 16 fiber equilibrium, 32 phase-3 rows, 64 implicit
-     * terms without a branch on h, 128 muscle eval) */
-    constexpr bool BF3 = !T::PLANAR && (IMP || BIOIM_BF3_RK);
-    constexpr bool BFK_FN = BFK || (BF3 && (BIOIM_BF3 & 1)), BFK_PATH = BFK || (BF3 && (BIOIM_BF3 & 2));
-    constexpr bool BFK_CON = BFK || (BF3 && (BIOIM_BF3 & 4)), BFK_LIM = BFK || (BF3 && (BIOIM_BF3 & 8));
-    constexpr bool BFK_EQ = BFK || (BF3 && (BIOIM_BF3 & 16)), BFK_ROW = BFK || (BF3 && (BIOIM_BF3 & 32));
-    constexpr bool BFK_ME = BFK || (BF3 && (BIOIM_BF3 & 128));
+    using SW = BfSwitch<T, IMP>;
     /* the muscle eval's curves and fiber-velocity solve in one block, in
      * every kernel (spatial too: no scratch; same-box 3D -1.6 %,
      * profiles/r03/r03k, r03l) */
@@ -1907,7 +1912,7 @@ DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Rea
                     s.vce = s.vN * mu.lv;
                     s.dvdl = cv[1];
                     s.clamped = cv[2] != Real(0);
-                    s.dadt = act_rate<BFK_ME>(mu, a, control[j]);
+                    s.dadt = act_rate<SW::ME>(mu, a, control[j]);
                 }
             }
         } else {
@@ -1944,7 +1949,7 @@ DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Rea
     /* ---- phase 0b: function slots, one lane each — the moving path points'
      * location functions (read by every muscle that has the point) and the
      * joints' spline axes (read by their body's lane) */
-    fn_slots<BFK_FN, T, Real>(SM, lds, lane);
+    fn_slots<SW::FN, T, Real>(SM, lds, lane);
     STAMP(15);
 
     /* ---- phase 1: lane-parallel kinematics */
@@ -2029,19 +2034,19 @@ DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Rea
             if (m < T::NM) {
                 const SMuscle<Real> &mu = SM.mus[m];
                 Real L, dLs[T::MAXSPAN];
-                muscle_path<BFK_PATH, T, Real>(SM, mu, lds, L, dLs);
+                muscle_path<SW::PATH, T, Real>(SM, mu, lds, L, dLs);
                 STAMP(4);
                 Real a_ = act[j], l_ = lce[j];
                 if (equilibrate) /* equilibrateMuscles: static fiber equilibrium at the held activation
                                   * (a reset has set the default activation) */
-                    l_ = muscle_equilibrium<BFK_EQ, T, Real>(SM, mu, a_, L);
+                    l_ = muscle_equilibrium<SW::EQ, T, Real>(SM, mu, a_, L);
                 D.act[j] = a_;
                 D.lce[j] = l_;
                 /* the sphere contacts ride in the first muscle pass (every
                  * sphere lane holds a muscle): same block as the curve
                  * evaluations, so their chains interleave */
-                if constexpr (j == 0 && MUSCLE_CONTACT) contact_compute<BFK_CON, T, Real>(SM, lds, lane < T::NS ? lane : 0, hi, CO);
-                muscle_eval<BFK_ME, BFC, T, Real>(SM, mu, a_, l_, control[j], L, D.ms[j].vN, D.ms[j]);
+                if constexpr (j == 0 && MUSCLE_CONTACT) contact_compute<SW::CON, T, Real>(SM, lds, lane < T::NS ? lane : 0, hi, CO);
+                muscle_eval<SW::ME, BFC, T, Real>(SM, mu, a_, l_, control[j], L, D.ms[j].vN, D.ms[j]);
                 const Real nFt = -D.ms[j].Ft;
                 Real *ts = lds + LY::TAU + (lane + j * G) * T::MAXSPAN;
 #pragma unroll
@@ -2061,20 +2066,20 @@ DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Rea
     if constexpr (MUSCLE_CONTACT) {
         if (lane < T::NS) contact_store<T, Real>(lds, lane, CO);
     } else {
-        if (lane < T::NS) contact_lane<BFK_CON, T, Real>(SM, lds, lane, hi);
+        if (lane < T::NS) contact_lane<SW::CON, T, Real>(SM, lds, lane, hi);
     }
     STAMP(6);
     if (lane < T::NL) {
         int cc = SM.lim_coord[lane];
         Real qv = lds[LY::QF + cc], qd = lds[LY::UF + cc];
         Real qup = SM.lim_qup[lane], qlo = SM.lim_qlow[lane], tr = SM.lim_trans[lane], itr = SM.lim_itrans[lane];
-        Real up = smooth_step<BFK_LIM>(Real(0), Real(1), qup, qup + tr, itr, qv);
-        Real lo = smooth_step<BFK_LIM>(Real(1), Real(0), qlo - tr, qlo, itr, qv);
+        Real up = smooth_step<SW::LIM>(Real(0), Real(1), qup, qup + tr, itr, qv);
+        Real lo = smooth_step<SW::LIM>(Real(1), Real(0), qlo - tr, qlo, itr, qv);
         Real f = -SM.lim_kup[lane] * up * (qv - qup) + SM.lim_klow[lane] * lo * (qlo - qv) - SM.lim_damp[lane] * (up + lo) * qd;
         Real diag = 0, tadd = f;
         if (IMP_BF || (!IMP_BF && hi > 0)) {   /* IMP_BF: no branch on h (at h = 0 this gives diag = 0, tadd = f) */
-            Real dup = smooth_step_d<BFK_LIM>(Real(0), Real(1), qup, qup + tr, itr, qv);
-            Real dlo = smooth_step_d<BFK_LIM>(Real(1), Real(0), qlo - tr, qlo, itr, qv);
+            Real dup = smooth_step_d<SW::LIM>(Real(0), Real(1), qup, qup + tr, itr, qv);
+            Real dlo = smooth_step_d<SW::LIM>(Real(1), Real(0), qlo - tr, qlo, itr, qv);
             Real kq = SM.lim_kup[lane] * (up + dup * (qv - qup)) + SM.lim_klow[lane] * (lo - dlo * (qlo - qv));
             Real cq = SM.lim_damp[lane] * (up + lo);
             diag = hi * cq + hi * hi * kq;
@@ -2151,7 +2156,7 @@ DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Rea
              * branch, two basic blocks per sphere */
             const bool onb = lds[LY::CW + 8 * sp + 6] > 0 && ((msk >> lane) & 1u);
             const Real on = onb ? Real(1) : Real(0);
-            if constexpr (BFK_ROW) r = fma(on, dot3m<ZV, 0>(jd, Fs), r);
+            if constexpr (SW::ROW) r = fma(on, dot3m<ZV, 0>(jd, Fs), r);
             else r += onb ? dot3m<ZV, 0>(jd, Fs) : Real(0);
             /* IMP (the semi-implicit kernels): no branch on h — a realize
              * call (h = 0) has C = 0 (contact_compute), adding zeros */
@@ -2162,7 +2167,7 @@ DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Rea
                 cross3(cj, w, pw);
 #pragma unroll
                 for (int i = 0; i < 3; ++i) {
-                    if constexpr (BFK_ROW) {
+                    if constexpr (SW::ROW) {
                         Gk[i] = fma(on, pw[i], Gk[i]);
                         Gk[3 + i] = fma(on, w[i], Gk[3 + i]);
                     } else {
@@ -2334,6 +2339,85 @@ DEV int draw_index(uint64_t seed, int env, int count, int hi) {
     return (int)(r % (uint64_t)(hi + 1));
 }
 
+/* ------------------------------------------- the analysis kernels' frame
+ * id / ma / so / ik / jr / ia_kernel share one launch shape and prologue:
+ * one state per T::G lanes, EPB states per workgroup (BIOIM_EPB; ia_kernel:
+ * IaLay::EPB), the SModel image staged into LDS in front of the states' Lay
+ * regions, then the env kernel's kinematics at the state's (q, u).  A
+ * kernel's arguments are the handle's model (ModelArgs) and the call's own
+ * list, a struct templated on its pointee type that follows the kernel: P =
+ * void is what the bioim_* entry point fills, P = Real (jr_kernel: IO) what
+ * the kernel takes (analysis_launch converts). */
+template <class T, typename Real> struct ModelArgs {
+    const DModel<Real> *Mg;
+    const SModel<T, Real> *Sg;
+};
+
+/* the model image into LDS by all EPB * G threads (before any lane exits), a barrier, the image */
+template <int EPB, class T, typename Real>
+DEV const SModel<T, Real> &stage_model(const SModel<T, Real> *Sg, unsigned char *smem_raw) {
+    const uint4 *src = reinterpret_cast<const uint4 *>(Sg);
+    uint4 *dst = reinterpret_cast<uint4 *>(smem_raw);
+    for (int i = threadIdx.x; i < (int)(smodel_bytes<T, Real>() / 16); i += EPB * T::G) dst[i] = src[i];
+    __syncthreads();
+    return *reinterpret_cast<const SModel<T, Real> *>(smem_raw);
+}
+
+/* dof lane: row idx of an optional [n][ND] input (IO: the caller's type), 0 where it is not given */
+template <typename Real, int ND, typename IO> DEV Real opt_row(const IO *p, int idx, int lane, int n) {
+    return p ? Real(GAT(p, (size_t)idx * ND + lane, (size_t)n * ND)) : Real(0);
+}
+
+/* The step's kinematics at (qd, ud) of the dof lanes, publish_coords through
+ * kin_column: frames (KB) and columns (S) are in LDS after the caller's next
+ * wave_sync (none here: id / jr / ia go on to body_inertia first).  FN: the
+ * fn_slots switch.  Returns x0, the shift of the ground origin. */
+template <bool FN, class T, typename Real>
+DEV Real state_kinematics(const DModel<Real> &M, const SModel<T, Real> &SM, Real *lds, int lane, Real qd, Real ud) {
+    using LY = Lay<T, Real>;
+    constexpr int ND = LY::ND, NB = T::NB;
+    publish_coords<T, Real>(M, SM, lds, lane, qd, ud);
+    if (lane < ND) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) lds[LY::SL + 6 * lane + i] = 0;
+    }
+    wave_sync();
+    Real x0 = 0;
+    if constexpr (T::TX >= 0) {
+        if constexpr (T::coord_dof[T::TX] >= 0) x0 = M.float_origin ? lds[LY::QF + T::TX] : Real(0);
+    }
+    fn_slots<FN, T, Real>(SM, lds, lane);
+    if (lane < NB) kin_local<T, Real>(SM, lds, lane);
+    if (lane == NB) kin_ground<T, Real>(lds, x0);
+    wave_sync();
+    if (lane < NB) kin_chain<T, Real>(SM, lds, lane, x0);
+    wave_sync();
+    if (lane < ND) kin_column<T, Real>(SM, lds, lane);
+    return x0;
+}
+
+/* body lane, after body_inertia: the body's gravity wrench (moment about the
+ * shifted origin, force) taken back out of WB, which then holds the velocity
+ * terms only; KEEP: the wrench itself goes to wg[6] (else wg is not read).
+ * The stores to wg stay between the updates of WB: with all of WB updated
+ * first the compiler forwards body_inertia's values into the sums and fuses
+ * them differently, which moved ia_kernel's results by some ulp */
+template <bool KEEP, class T, typename Real>
+DEV void gravity_wrench_out(const DModel<Real> &M, const SModel<T, Real> &SM, Real *lds, int lane, Real *wg) {
+    using LY = Lay<T, Real>;
+    const Real *kb = lds + LY::KB + 18 * lane;
+    Real cG[3], mg[3], t[3];
+    mv3(kb, SM.body[lane].com, cG);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { cG[i] += kb[9 + i]; mg[i] = SM.body[lane].mass * M.gravity[i]; }
+    cross3(cG, mg, t);
+    Real *wb = lds + LY::WB + 6 * lane;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        wb[i] += t[i]; wb[3 + i] += mg[i];
+        if constexpr (KEEP) { wg[i] = t[i]; wg[3 + i] = mg[i]; }
+    }
+}
 
 /* ------------------------------------------------- inverse dynamics
  * Batched primitives of the reference's Boost.Python InverseDynamics helper
@@ -2348,32 +2432,24 @@ DEV int draw_index(uint64_t seed, int env, int count, int hi) {
  *   TOTAL     c - f_applied(q, u)  (M q'' + f = tau)        (:96-125)
  * f_applied = gravity + Hunt-Crossley contact + coordinate limit forces
  * (generalized).  Vectors are [n][ndof] in dof order. */
-template <class T, typename Real> struct IdArgs {
-    const DModel<Real> *Mg;
-    const SModel<T, Real> *Sg;
+template <typename P> struct IdFields {   /* bioim_inverse_dynamics */
     int n, op;
-    const Real *q, *u, *v;
-    Real *out;
+    const P *q, *u, *v;
+    P *out;
 };
 
 template <class T, typename Real>
 #ifndef BIOIM_ID_NO_WAVES_ATTR
-__global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_eu(1, 1))) void id_kernel(IdArgs<T, Real> a) {
+__global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_eu(1, 1))) void id_kernel(ModelArgs<T, Real> md, IdFields<Real> a) {
 #else   /* the compiler-crash reproducer (profiles/r03/regalloc_crash/): without the occupancy attribute */
-__global__ __launch_bounds__(BIOIM_EPB * T::G) void id_kernel(IdArgs<T, Real> a) {
+__global__ __launch_bounds__(BIOIM_EPB * T::G) void id_kernel(ModelArgs<T, Real> md, IdFields<Real> a) {
 #endif
     using LY = Lay<T, Real>;
     constexpr int G = T::G, ND = LY::ND, NB = T::NB, NP = LY::NP, EPB = BIOIM_EPB;
     constexpr size_t SMB = smodel_bytes<T, Real>();
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    {
-        const uint4 *src = reinterpret_cast<const uint4 *>(a.Sg);
-        uint4 *dst = reinterpret_cast<uint4 *>(smem_raw);
-        for (int i = threadIdx.x; i < (int)(SMB / 16); i += BIOIM_EPB * G) dst[i] = src[i];
-    }
-    __syncthreads();
-    const SModel<T, Real> &SM = *reinterpret_cast<const SModel<T, Real> *>(smem_raw);
-    const DModel<Real> &M = *a.Mg;
+    const SModel<T, Real> &SM = stage_model<EPB, T, Real>(md.Sg, smem_raw);
+    const DModel<Real> &M = *md.Mg;
     const int lane = threadIdx.x % G, slot = threadIdx.x / G;
     const int idx = blockIdx.x * EPB + slot;
     if (idx >= a.n) return;
@@ -2388,36 +2464,10 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) void id_kernel(IdArgs<T, Real> a)
         ud = use_u ? GAT(a.u, (size_t)idx * ND + lane, (size_t)a.n * ND) : Real(0);
         vd = (need_m || op == BIOIM_ID_MULT_MINV) ? GAT(a.v, (size_t)idx * ND + lane, (size_t)a.n * ND) : Real(0);
     }
-    publish_coords<T, Real>(M, SM, lds, lane, qd, ud);
-    if (lane < ND) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) lds[LY::SL + 6 * lane + i] = 0;
-    }
-    wave_sync();
-    Real x0 = 0;
-    if constexpr (T::TX >= 0) {
-        if constexpr (T::coord_dof[T::TX] >= 0) x0 = M.float_origin ? lds[LY::QF + T::TX] : Real(0);
-    }
-    fn_slots<false, T, Real>(SM, lds, lane);
-    if (lane < NB) kin_local<T, Real>(SM, lds, lane);
-    if (lane == NB) kin_ground<T, Real>(lds, x0);
-    wave_sync();
-    if (lane < NB) kin_chain<T, Real>(SM, lds, lane, x0);
-    wave_sync();
-    if (lane < ND) kin_column<T, Real>(SM, lds, lane);
+    state_kinematics<false, T, Real>(M, SM, lds, lane, qd, ud);
     if (lane < NB) {
         body_inertia<T, Real>(SM, M, lds, lane);
-        if (op == BIOIM_ID_CORIOLIS) {   /* velocity terms only: take the gravity wrench back out */
-            const Real *kb = lds + LY::KB + 18 * lane;
-            Real cG[3], mg[3], t[3];
-            mv3(kb, SM.body[lane].com, cG);
-#pragma unroll
-            for (int i = 0; i < 3; ++i) { cG[i] += kb[9 + i]; mg[i] = SM.body[lane].mass * M.gravity[i]; }
-            cross3(cG, mg, t);
-            Real *wb = lds + LY::WB + 6 * lane;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) { wb[i] += t[i]; wb[3 + i] += mg[i]; }
-        }
+        if (op == BIOIM_ID_CORIOLIS) gravity_wrench_out<false, T, Real>(M, SM, lds, lane, nullptr);   /* velocity terms only */
     }
     wave_sync();
     {   /* subtree sums of inertia and wrench (all reads, then all writes) */
@@ -2542,33 +2592,22 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) void id_kernel(IdArgs<T, Real> a)
  * cold fiber-velocity start.  -F_t dL/dq goes to the step's TAU slots and the
  * dof lanes gather it through SM.tau_src in the step's order.  Nothing of the
  * env state is read or written.  Any output may be null. */
-template <class T, typename Real> struct MaArgs {
-    const DModel<Real> *Mg;
-    const SModel<T, Real> *Sg;
+template <typename P> struct MaFields {   /* bioim_muscle_eval */
     int n;
-    const Real *q, *u, *act, *lce;
-    Real *length, *speed, *dldq, *fiber, *tau;
+    const P *q, *u, *act, *lce;
+    P *length, *speed, *dldq, *fiber, *tau;
 };
 
 template <class T, typename Real>
-__global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_eu(1, 1))) void ma_kernel(MaArgs<T, Real> a) {
+__global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_eu(1, 1))) void ma_kernel(ModelArgs<T, Real> md, MaFields<Real> a) {
     using LY = Lay<T, Real>;
-    constexpr int G = T::G, ND = LY::ND, NB = T::NB, NM = T::NM, MPL = LY::MPL, NSP = T::MAXSPAN, EPB = BIOIM_EPB;
+    using SW = BfSwitch<T>;   /* the step's switches (dynamics(), semi-implicit kernels) */
+    constexpr int G = T::G, ND = LY::ND, NM = T::NM, MPL = LY::MPL, NSP = T::MAXSPAN, EPB = BIOIM_EPB;
     constexpr size_t SMB = smodel_bytes<T, Real>();
     static_assert(NM > 0, "muscle topologies only");
-    /* the step's switches (dynamics(), semi-implicit kernels) */
-    constexpr bool BFK = T::PLANAR || BIOIM_BF_SPATIAL, BF3 = !T::PLANAR;
-    constexpr bool BFK_FN = BFK || (BF3 && (BIOIM_BF3 & 1)), BFK_PATH = BFK || (BF3 && (BIOIM_BF3 & 2));
-    constexpr bool BFK_EQ = BFK || (BF3 && (BIOIM_BF3 & 16)), BFK_ME = BFK || (BF3 && (BIOIM_BF3 & 128));
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    {
-        const uint4 *src = reinterpret_cast<const uint4 *>(a.Sg);
-        uint4 *dst = reinterpret_cast<uint4 *>(smem_raw);
-        for (int i = threadIdx.x; i < (int)(SMB / 16); i += BIOIM_EPB * G) dst[i] = src[i];
-    }
-    __syncthreads();
-    const SModel<T, Real> &SM = *reinterpret_cast<const SModel<T, Real> *>(smem_raw);
-    const DModel<Real> &M = *a.Mg;
+    const SModel<T, Real> &SM = stage_model<EPB, T, Real>(md.Sg, smem_raw);
+    const DModel<Real> &M = *md.Mg;
     const int lane = threadIdx.x % G, slot = threadIdx.x / G;
     const int idx = blockIdx.x * EPB + slot;
     if (idx >= a.n) return;
@@ -2576,25 +2615,9 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_e
     Real qd = 0, ud = 0;
     if (lane < ND) {
         qd = GAT(a.q, (size_t)idx * ND + lane, (size_t)a.n * ND);
-        ud = a.u ? GAT(a.u, (size_t)idx * ND + lane, (size_t)a.n * ND) : Real(0);
+        ud = opt_row<Real, ND>(a.u, idx, lane, a.n);
     }
-    publish_coords<T, Real>(M, SM, lds, lane, qd, ud);
-    if (lane < ND) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) lds[LY::SL + 6 * lane + i] = 0;
-    }
-    wave_sync();
-    Real x0 = 0;
-    if constexpr (T::TX >= 0) {
-        if constexpr (T::coord_dof[T::TX] >= 0) x0 = M.float_origin ? lds[LY::QF + T::TX] : Real(0);
-    }
-    fn_slots<BFK_FN, T, Real>(SM, lds, lane);
-    if (lane < NB) kin_local<T, Real>(SM, lds, lane);
-    if (lane == NB) kin_ground<T, Real>(lds, x0);
-    wave_sync();
-    if (lane < NB) kin_chain<T, Real>(SM, lds, lane, x0);
-    wave_sync();
-    if (lane < ND) kin_column<T, Real>(SM, lds, lane);
+    state_kinematics<SW::FN, T, Real>(M, SM, lds, lane, qd, ud);
     wave_sync();   /* the columns are out, and the joint-local region (LOC / SL) the TAU slots share is free */
     const bool fib = a.act != nullptr;
     if (lane == 0) lds[LY::TAU + LY::TZ] = Real(0);
@@ -2605,7 +2628,7 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_e
             const SMuscle<Real> &mu = SM.mus[m];
             const size_t row = (size_t)idx * NM + m, rows = (size_t)a.n * NM;
             Real L, dLs[NSP];
-            muscle_path<BFK_PATH, T, Real>(SM, mu, lds, L, dLs);
+            muscle_path<SW::PATH, T, Real>(SM, mu, lds, L, dLs);
             if (a.length) GAT(a.length, row, rows) = L;
             if (a.speed) {
                 Real s = 0;
@@ -2631,9 +2654,9 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_e
                 const Real a_ = GAT(a.act, row, rows);
                 Real l_;
                 if (a.lce) l_ = GAT(a.lce, row, rows);
-                else l_ = muscle_equilibrium<BFK_EQ, T, Real>(SM, mu, a_, L);
+                else l_ = muscle_equilibrium<SW::EQ, T, Real>(SM, mu, a_, L);
                 MState<Real> ms;
-                muscle_eval<BFK_ME, true, T, Real>(SM, mu, a_, l_, a_, L, Real(0), ms);
+                muscle_eval<SW::ME, true, T, Real>(SM, mu, a_, l_, a_, L, Real(0), ms);
                 if (a.fiber) {
                     Real *f = a.fiber + GIDX(row * BIOIM_MUSCLE_FIBER_DIM, rows * BIOIM_MUSCLE_FIBER_DIM);
                     f[0] = ms.lce; f[1] = ms.vce; f[2] = ms.Ft; f[3] = ms.Ff; f[4] = ms.Fa;
@@ -2706,13 +2729,11 @@ template <int G, typename V> DEV V group_min(V x) {
     return x;
 }
 
-template <class T, typename Real> struct SoArgs {
-    const DModel<Real> *Mg;
-    const SModel<T, Real> *Sg;
+template <typename P> struct SoFields {   /* bioim_static_opt (fp64 only) */
     int n, passive;
-    const Real *q, *u, *tau, *row_weight;
-    Real lo, hi;
-    Real *act, *residual, *tau_muscle, *capacity;
+    const P *q, *u, *tau, *row_weight;
+    double lo, hi;
+    P *act, *residual, *tau_muscle, *capacity;
     int32_t *status;
 };
 
@@ -2770,24 +2791,17 @@ DEV void muscle_rigid_capacity(const SModel<T, Real> &SM, const SMuscle<Real> &m
 }
 
 template <class T, typename Real>
-__global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_eu(1, 1))) void so_kernel(SoArgs<T, Real> a) {
+__global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_eu(1, 1))) void so_kernel(ModelArgs<T, Real> md, SoFields<Real> a) {
     using LY = Lay<T, Real>;
     using SL = SoLay<T, Real>;
-    constexpr int G = T::G, ND = LY::ND, NB = T::NB, NM = T::NM, MPL = LY::MPL, NSP = T::MAXSPAN, EPB = BIOIM_EPB;
+    using SW = BfSwitch<T>;
+    constexpr int G = T::G, ND = LY::ND, NM = T::NM, MPL = LY::MPL, NSP = T::MAXSPAN, EPB = BIOIM_EPB;
     constexpr int NH = SL::NH;
     constexpr size_t SMB = smodel_bytes<T, Real>();
     static_assert(NM > 0, "muscle topologies only");
-    constexpr bool BFK = T::PLANAR || BIOIM_BF_SPATIAL, BF3 = !T::PLANAR;
-    constexpr bool BFK_FN = BFK || (BF3 && (BIOIM_BF3 & 1)), BFK_PATH = BFK || (BF3 && (BIOIM_BF3 & 2));
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    {
-        const uint4 *src = reinterpret_cast<const uint4 *>(a.Sg);
-        uint4 *dst = reinterpret_cast<uint4 *>(smem_raw);
-        for (int i = threadIdx.x; i < (int)(SMB / 16); i += BIOIM_EPB * G) dst[i] = src[i];
-    }
-    __syncthreads();
-    const SModel<T, Real> &SM = *reinterpret_cast<const SModel<T, Real> *>(smem_raw);
-    const DModel<Real> &M = *a.Mg;
+    const SModel<T, Real> &SM = stage_model<EPB, T, Real>(md.Sg, smem_raw);
+    const DModel<Real> &M = *md.Mg;
     const int lane = threadIdx.x % G, slot = threadIdx.x / G;
     const int idx = blockIdx.x * EPB + slot;
     if (idx >= a.n) return;
@@ -2795,25 +2809,9 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_e
     Real qd = 0, ud = 0;
     if (lane < ND) {
         qd = GAT(a.q, (size_t)idx * ND + lane, (size_t)a.n * ND);
-        ud = a.u ? GAT(a.u, (size_t)idx * ND + lane, (size_t)a.n * ND) : Real(0);
+        ud = opt_row<Real, ND>(a.u, idx, lane, a.n);
     }
-    publish_coords<T, Real>(M, SM, lds, lane, qd, ud);
-    if (lane < ND) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) lds[LY::SL + 6 * lane + i] = 0;
-    }
-    wave_sync();
-    Real x0 = 0;
-    if constexpr (T::TX >= 0) {
-        if constexpr (T::coord_dof[T::TX] >= 0) x0 = M.float_origin ? lds[LY::QF + T::TX] : Real(0);
-    }
-    fn_slots<BFK_FN, T, Real>(SM, lds, lane);
-    if (lane < NB) kin_local<T, Real>(SM, lds, lane);
-    if (lane == NB) kin_ground<T, Real>(lds, x0);
-    wave_sync();
-    if (lane < NB) kin_chain<T, Real>(SM, lds, lane, x0);
-    wave_sync();
-    if (lane < ND) kin_column<T, Real>(SM, lds, lane);
+    state_kinematics<SW::FN, T, Real>(M, SM, lds, lane, qd, ud);
     wave_sync();   /* the columns are out, and the joint-local region (LOC / SL) the slot arrays share is free */
     const bool passive = a.passive != 0;
     const Real lo = a.lo, hi = a.hi;
@@ -2832,7 +2830,7 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_e
         if (m < NM) {
             const SMuscle<Real> &mu = SM.mus[m];
             Real L, dLs[NSP];
-            muscle_path<BFK_PATH, T, Real>(SM, mu, lds, L, dLs);
+            muscle_path<SW::PATH, T, Real>(SM, mu, lds, L, dLs);
             /* a dof that moves every point of the path moves it rigidly: dL/dq is
              * exactly 0 there (the sum over the path vanishes, as on the floating
              * base, which the span leaves out for that reason), unless a moving
@@ -3170,14 +3168,12 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_e
  * wave_sync orders the LDS traffic, and no workgroup barrier follows the
  * idx >= n exit.  No atomics, sums in a fixed order: a frame's result does
  * not depend on n or its neighbours. */
-template <class T, typename Real> struct IkArgs {
-    const DModel<Real> *Mg;
-    const SModel<T, Real> *Sg;
+template <typename P> struct IkFields {   /* bioim_ik_solve (fp64 only) */
     int n, nm, max_iter;
     const int32_t *marker_body;
-    const Real *marker_loc, *weight, *x_exp, *q0, *coord_weight, *q_target;
-    Real tol;
-    Real *q, *markers, *err, *jacobian;
+    const P *marker_loc, *weight, *x_exp, *q0, *coord_weight, *q_target;
+    double tol;
+    P *q, *markers, *err, *jacobian;
     int32_t *status;
 };
 
@@ -3201,24 +3197,16 @@ template <class T, typename Real> struct IkLay {
 };
 
 template <class T, typename Real>
-__global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_eu(1, 1))) void ik_kernel(IkArgs<T, Real> a) {
+__global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_eu(1, 1))) void ik_kernel(ModelArgs<T, Real> md, IkFields<Real> a) {
     using LY = Lay<T, Real>;
     using PL = Planar<T>;
     using IK = IkLay<T, Real>;
-    constexpr int G = T::G, ND = LY::ND, NB = T::NB, NP = LY::NP, EPB = BIOIM_EPB;
+    constexpr int G = T::G, ND = LY::ND, NP = LY::NP, EPB = BIOIM_EPB;
     constexpr size_t SMB = smodel_bytes<T, Real>();
     static_assert(LY::RHS == LY::MP + NP, "g is row ND of the packed matrix");
-    constexpr bool BFK = T::PLANAR || BIOIM_BF_SPATIAL, BF3 = !T::PLANAR;
-    constexpr bool BFK_FN = BFK || (BF3 && (BIOIM_BF3 & 1));
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    {
-        const uint4 *src = reinterpret_cast<const uint4 *>(a.Sg);
-        uint4 *dst = reinterpret_cast<uint4 *>(smem_raw);
-        for (int i = threadIdx.x; i < (int)(SMB / 16); i += BIOIM_EPB * G) dst[i] = src[i];
-    }
-    __syncthreads();
-    const SModel<T, Real> &SM = *reinterpret_cast<const SModel<T, Real> *>(smem_raw);
-    const DModel<Real> &M = *a.Mg;
+    const SModel<T, Real> &SM = stage_model<EPB, T, Real>(md.Sg, smem_raw);
+    const DModel<Real> &M = *md.Mg;
     const int lane = threadIdx.x % G, slot = threadIdx.x / G;
     const int idx = blockIdx.x * EPB + slot;
     if (idx >= a.n) return;
@@ -3283,23 +3271,7 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_e
     };
     while (true) {
         /* the kinematics prologue at the trial point */
-        publish_coords<T, Real>(M, SM, lds, lane, qt, Real(0));
-        if (lane < ND) {
-#pragma unroll
-            for (int i = 0; i < 6; ++i) lds[LY::SL + 6 * lane + i] = 0;
-        }
-        wave_sync();
-        Real x0 = 0;
-        if constexpr (T::TX >= 0) {
-            if constexpr (T::coord_dof[T::TX] >= 0) x0 = M.float_origin ? lds[LY::QF + T::TX] : Real(0);
-        }
-        fn_slots<BFK_FN, T, Real>(SM, lds, lane);
-        if (lane < NB) kin_local<T, Real>(SM, lds, lane);
-        if (lane == NB) kin_ground<T, Real>(lds, x0);
-        wave_sync();
-        if (lane < NB) kin_chain<T, Real>(SM, lds, lane, x0);
-        wave_sync();
-        if (lane < ND) kin_column<T, Real>(SM, lds, lane);
+        const Real x0 = state_kinematics<BfSwitch<T>::FN, T, Real>(M, SM, lds, lane, qt, Real(0));
         wave_sync();   /* frames and columns are out; the union region (LOC / SL) is free until the next prologue */
         if (fin) {
             /* the outputs at the returned q */
@@ -3509,12 +3481,10 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_e
  * to fp32 costs.  An fp32 handle therefore gets a second, fp64 model image
  * on its first call (jr_fp64_model) and converts only at the kernel's loads
  * and stores. */
-template <class T, typename IO> struct JrArgs {
-    const DModel<double> *Mg;
-    const SModel<T, double> *Sg;
+template <typename P> struct JrFields {   /* bioim_joint_reaction */
     int n, flags, frame;
-    const IO *q, *u, *qdd, *ft, *ext;
-    IO *reaction, *point, *tau_joint, *muscle_wrench;
+    const P *q, *u, *qdd, *ft, *ext;
+    P *reaction, *point, *tau_joint, *muscle_wrench;
 };
 
 /* The point forces of one muscle at tendon force Ft, summed per composite
@@ -3616,20 +3586,14 @@ DEV void muscle_point_wrench(const SModel<T, Real> &SM, const SMuscle<Real> &mu,
 }
 
 template <class T, typename IO>
-__global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_eu(1, 1))) void jr_kernel(JrArgs<T, IO> a) {
+__global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_eu(1, 1))) void jr_kernel(ModelArgs<T, double> md, JrFields<IO> a) {
     using Real = double;
     using LY = Lay<T, Real>;
     constexpr int G = T::G, ND = LY::ND, NB = T::NB, NM = T::NM, EPB = BIOIM_EPB;
     constexpr size_t SMB = smodel_bytes<T, Real>();
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    {
-        const uint4 *src = reinterpret_cast<const uint4 *>(a.Sg);
-        uint4 *dst = reinterpret_cast<uint4 *>(smem_raw);
-        for (int i = threadIdx.x; i < (int)(SMB / 16); i += BIOIM_EPB * G) dst[i] = src[i];
-    }
-    __syncthreads();
-    const SModel<T, Real> &SM = *reinterpret_cast<const SModel<T, Real> *>(smem_raw);
-    const DModel<Real> &M = *a.Mg;
+    const SModel<T, Real> &SM = stage_model<EPB, T, Real>(md.Sg, smem_raw);
+    const DModel<Real> &M = *md.Mg;
     const int lane = threadIdx.x % G, slot = threadIdx.x / G;
     const int idx = blockIdx.x * EPB + slot;
     if (idx >= a.n) return;
@@ -3638,26 +3602,10 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_e
     Real qd = 0, ud = 0, ad = 0;
     if (lane < ND) {
         qd = GAT(a.q, (size_t)idx * ND + lane, (size_t)a.n * ND);
-        ud = a.u ? GAT(a.u, (size_t)idx * ND + lane, (size_t)a.n * ND) : Real(0);
-        ad = a.qdd ? GAT(a.qdd, (size_t)idx * ND + lane, (size_t)a.n * ND) : Real(0);
+        ud = opt_row<Real, ND>(a.u, idx, lane, a.n);
+        ad = opt_row<Real, ND>(a.qdd, idx, lane, a.n);
     }
-    publish_coords<T, Real>(M, SM, lds, lane, qd, ud);
-    if (lane < ND) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) lds[LY::SL + 6 * lane + i] = 0;
-    }
-    wave_sync();
-    Real x0 = 0;
-    if constexpr (T::TX >= 0) {
-        if constexpr (T::coord_dof[T::TX] >= 0) x0 = M.float_origin ? lds[LY::QF + T::TX] : Real(0);
-    }
-    fn_slots<false, T, Real>(SM, lds, lane);
-    if (lane < NB) kin_local<T, Real>(SM, lds, lane);
-    if (lane == NB) kin_ground<T, Real>(lds, x0);
-    wave_sync();
-    if (lane < NB) kin_chain<T, Real>(SM, lds, lane, x0);
-    wave_sync();
-    if (lane < ND) kin_column<T, Real>(SM, lds, lane);
+    const Real x0 = state_kinematics<false, T, Real>(M, SM, lds, lane, qd, ud);
     if (lane < NB) body_inertia<T, Real>(SM, M, lds, lane);
     if (lane < ND) lds[LY::RHS + lane] = ad;
     wave_sync();   /* columns, inertias and wrenches are out; the joint-local region the CJ slots share is free */
@@ -3852,14 +3800,12 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_e
  * A pivot <= 0 or a NaN (M, S, or the total column) gives status -2 and zero
  * outputs.  No atomics, no shared slot written at a run-time index (a lane
  * writes only columns it owns), every sum in a fixed order. */
-template <class T, typename Real> struct IaArgs {
-    const DModel<Real> *Mg;
-    const SModel<T, Real> *Sg;
+template <typename P> struct IaFields {   /* bioim_induced_accel (fp64 only) */
     int n, kind;
-    Real thr;
-    const Real *q, *u, *ft, *tau_act, *ext, *cpoint;
+    double thr;
+    const P *q, *u, *ft, *tau_act, *ext, *cpoint;
     const uint8_t *cactive;
-    Real *accel, *com_accel, *reaction, *cpoint_out;
+    P *accel, *com_accel, *reaction, *cpoint_out;
     uint8_t *cactive_out;
     int32_t *status;
 };
@@ -3904,24 +3850,19 @@ template <class T, typename Real> struct IaLay {
 };
 
 template <class T, typename Real>
-__global__ __launch_bounds__((IaLay<T, Real>::EPB * T::G)) __attribute__((amdgpu_waves_per_eu(1, 1))) void ia_kernel(IaArgs<T, Real> a) {
+__global__ __launch_bounds__((IaLay<T, Real>::EPB * T::G)) __attribute__((amdgpu_waves_per_eu(1, 1))) void ia_kernel(ModelArgs<T, Real> md, IaFields<Real> a) {
     using LY = Lay<T, Real>;
     using IA = IaLay<T, Real>;
     using PL = Planar<T>;
+    using SW = BfSwitch<T>;
     constexpr int G = T::G, ND = LY::ND, NB = T::NB, NM = T::NM, NF = T::NF, EPB = IA::EPB;
     constexpr int NCOL = IA::NCOL, NR = IA::NR, NJ = IA::NJ;
     constexpr int C_CON = 2, C_LIM = 2 + NF, C_ACT = 3 + NF, C_EXT = 4 + NF, C_MUS = 5 + NF, C_TOT = NCOL - 1;
     constexpr size_t SMB = smodel_bytes<T, Real>();
     static_assert(NB < G && NF <= G && NJ <= G, "body, foot and constraint-row lanes");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    {
-        const uint4 *src = reinterpret_cast<const uint4 *>(a.Sg);
-        uint4 *dst = reinterpret_cast<uint4 *>(smem_raw);
-        for (int i = threadIdx.x; i < (int)(SMB / 16); i += EPB * G) dst[i] = src[i];
-    }
-    __syncthreads();
-    const SModel<T, Real> &SM = *reinterpret_cast<const SModel<T, Real> *>(smem_raw);
-    const DModel<Real> &M = *a.Mg;
+    const SModel<T, Real> &SM = stage_model<EPB, T, Real>(md.Sg, smem_raw);
+    const DModel<Real> &M = *md.Mg;
     const int lane = threadIdx.x % G, slot = threadIdx.x / G;
     const int idx = blockIdx.x * EPB + slot;
     if (idx >= a.n) return;
@@ -3931,39 +3872,14 @@ __global__ __launch_bounds__((IaLay<T, Real>::EPB * T::G)) __attribute__((amdgpu
     Real qd = 0, ud = 0;
     if (lane < ND) {
         qd = GAT(a.q, (size_t)idx * ND + lane, (size_t)a.n * ND);
-        ud = a.u ? GAT(a.u, (size_t)idx * ND + lane, (size_t)a.n * ND) : Real(0);
+        ud = opt_row<Real, ND>(a.u, idx, lane, a.n);
     }
-    publish_coords<T, Real>(M, SM, lds, lane, qd, ud);
-    if (lane < ND) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) lds[LY::SL + 6 * lane + i] = 0;
-    }
-    wave_sync();
-    Real x0 = 0;
-    if constexpr (T::TX >= 0) {
-        if constexpr (T::coord_dof[T::TX] >= 0) x0 = M.float_origin ? lds[LY::QF + T::TX] : Real(0);
-    }
-    constexpr bool BFK = T::PLANAR || BIOIM_BF_SPATIAL, BF3 = !T::PLANAR;
-    constexpr bool BFK_FN = BFK || (BF3 && (BIOIM_BF3 & 1)), BFK_PATH = BFK || (BF3 && (BIOIM_BF3 & 2));
-    fn_slots<(NM > 0 ? BFK_FN : false), T, Real>(SM, lds, lane);
-    if (lane < NB) kin_local<T, Real>(SM, lds, lane);
-    if (lane == NB) kin_ground<T, Real>(lds, x0);
-    wave_sync();
-    if (lane < NB) kin_chain<T, Real>(SM, lds, lane, x0);
-    wave_sync();
-    if (lane < ND) kin_column<T, Real>(SM, lds, lane);
+    const Real x0 = state_kinematics<(NM > 0 ? SW::FN : false), T, Real>(M, SM, lds, lane, qd, ud);
     if (lane < NB) {
         body_inertia<T, Real>(SM, M, lds, lane);
-        /* the gravity wrench out of WB (id_kernel's CORIOLIS form) into WG; ext about the shifted origin into XW */
-        const Real *kb = lds + LY::KB + 18 * lane;
-        Real cG[3], mg[3], t[3];
-        mv3(kb, SM.body[lane].com, cG);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) { cG[i] += kb[9 + i]; mg[i] = SM.body[lane].mass * M.gravity[i]; }
-        cross3(cG, mg, t);
-        Real *wb = lds + LY::WB + 6 * lane, *wg = tl + IA::WG + 6 * lane, *xw = tl + IA::XW + 6 * lane;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) { wb[i] += t[i]; wb[3 + i] += mg[i]; wg[i] = t[i]; wg[3 + i] = mg[i]; }
+        /* the gravity wrench out of WB into WG; ext about the shifted origin into XW */
+        gravity_wrench_out<true, T, Real>(M, SM, lds, lane, tl + IA::WG + 6 * lane);
+        Real *xw = tl + IA::XW + 6 * lane;
         Real e[6] = {0, 0, 0, 0, 0, 0};
         if (a.ext) {
 #pragma unroll
@@ -4133,7 +4049,7 @@ __global__ __launch_bounds__((IaLay<T, Real>::EPB * T::G)) __attribute__((amdgpu
         for (int li = 0; li < T::NL; ++li)
             if (SM.lim_dof[li] == lane) lim += lds[LY::LIM + 4 * li];
         col[C_LIM * ND] = lim;
-        col[C_ACT * ND] = a.tau_act ? GAT(a.tau_act, (size_t)idx * ND + lane, (size_t)a.n * ND) : Real(0);
+        col[C_ACT * ND] = opt_row<Real, ND>(a.tau_act, idx, lane, a.n);
         col[C_EXT * ND] = dot3(Sd, xw) + dot3(Sd + 3, xw + 3);
     }
     if (lane < NF) {
@@ -4169,7 +4085,7 @@ __global__ __launch_bounds__((IaLay<T, Real>::EPB * T::G)) __attribute__((amdgpu
             if (m < NM) {
                 const SMuscle<Real> &mu = SM.mus[m];
                 Real L, dLs[NSP];
-                muscle_path<BFK_PATH, T, Real>(SM, mu, lds, L, dLs);
+                muscle_path<SW::PATH, T, Real>(SM, mu, lds, L, dLs);
                 const Real nFt = a.ft ? -GAT(a.ft, (size_t)idx * NM + m, (size_t)a.n * NM) : Real(0);
                 Real *col = tl + IA::COL + (C_MUS + m) * ND;   /* this lane's own column */
 #pragma unroll
@@ -6183,50 +6099,6 @@ struct RolloutCall {   /* bioim_rollout's arguments (untyped), for Ops::rollout 
     int stop_at_done;
 };
 
-struct MuscleEvalCall {   /* bioim_muscle_eval's arguments (untyped), for Ops::ma_launch */
-    int n;
-    const void *q, *u, *act, *lce;
-    void *length, *speed, *dldq, *fiber, *tau;
-};
-
-struct StaticOptCall {   /* bioim_static_opt's arguments (untyped), for Ops::so_launch */
-    int n;
-    const void *q, *u, *tau, *row_weight;
-    double lo, hi;
-    int passive;
-    void *act, *residual, *tau_muscle, *capacity;
-    int32_t *status;
-};
-
-struct IkCall {   /* bioim_ik_solve's arguments (untyped), for Ops::ik_launch */
-    int n, nm;
-    const int32_t *marker_body;
-    const void *marker_loc, *weight, *x_exp, *q0, *coord_weight, *q_target;
-    double tol;
-    int max_iter;
-    void *q, *markers, *err, *jacobian;
-    int32_t *status;
-};
-
-struct JrCall {   /* bioim_joint_reaction's arguments (untyped), for Ops::jr_launch */
-    int n;
-    const void *q, *u, *qdd, *ft, *ext;
-    int flags, frame;
-    void *reaction, *point, *tau_joint, *muscle_wrench;
-};
-
-struct IaCall {   /* bioim_induced_accel's arguments (untyped), for Ops::ia_launch */
-    int n;
-    const void *q, *u, *ft, *tau_act, *ext;
-    int kind;
-    const uint8_t *cactive;
-    const void *cpoint;
-    double force_threshold;
-    void *accel, *com_accel, *reaction, *cpoint_out;
-    uint8_t *cactive_out;
-    int32_t *status;
-};
-
 struct Ops {
     const char *topo;   /* the topology struct's name (fused-pair lookup) */
     int lanes;
@@ -6235,17 +6107,18 @@ struct Ops {
     int (*upload)(bioim_handle_t *);
     void (*launch)(bioim_handle_t *, int mode, const void *actions, void *obs, void *reward, uint8_t *done, void *info,
                    const int32_t *env_ids, const int32_t *ref_index, int n_list, const OsimCall *oc);
-    void (*id_launch)(bioim_handle_t *, int op, int n, const void *q, const void *u, const void *v, void *out);
+    /* the analysis launchers take the entry point's arguments as the kernel's own list with void pointees */
+    void (*id_launch)(bioim_handle_t *, const IdFields<void> &);
     /* bioim_muscle_eval's launcher; null for a torque topology (no muscles, no kernel) */
-    void (*ma_launch)(bioim_handle_t *, const MuscleEvalCall &);
+    void (*ma_launch)(bioim_handle_t *, const MaFields<void> &);
     /* bioim_static_opt's launcher; null for a torque topology and for an fp32 handle (fp64 kernels only) */
-    void (*so_launch)(bioim_handle_t *, const StaticOptCall &);
+    void (*so_launch)(bioim_handle_t *, const SoFields<void> &);
     /* bioim_ik_solve's launcher (every topology); null for an fp32 handle (fp64 kernels only) */
-    void (*ik_launch)(bioim_handle_t *, const IkCall &);
+    void (*ik_launch)(bioim_handle_t *, const IkFields<void> &);
     /* bioim_joint_reaction's launcher (every topology, both precisions); < 0: the fp64 image's upload failed */
-    int (*jr_launch)(bioim_handle_t *, const JrCall &);
+    int (*jr_launch)(bioim_handle_t *, const JrFields<void> &);
     /* bioim_induced_accel's launcher (every topology); null for an fp32 handle (fp64 kernels only) */
-    void (*ia_launch)(bioim_handle_t *, const IaCall &);
+    void (*ia_launch)(bioim_handle_t *, const IaFields<void> &);
     /* the fused rollout kernel's launcher; null where that instantiation is
      * left out (bioim_rollout then loops over `launch`) */
     void (*rollout)(bioim_handle_t *, const RolloutCall &);
@@ -6496,69 +6369,46 @@ int rollout2_launch_impl(bioim_handle_t *h0, size_t off0, bioim_handle_t *h1, si
     return 0;
 }
 
-template <class T, typename Real>
-void id_launch_impl(bioim_handle_t *h, int op, int n, const void *q, const void *u, const void *v, void *out) {
-    constexpr int EPB = BIOIM_EPB;
-    IdArgs<T, Real> a;
-    a.Mg = reinterpret_cast<const DModel<Real> *>(h->model);
-    a.Sg = reinterpret_cast<const SModel<T, Real> *>(h->smodel);
-    a.n = n; a.op = op;
-    a.q = reinterpret_cast<const Real *>(q); a.u = reinterpret_cast<const Real *>(u);
-    a.v = reinterpret_cast<const Real *>(v); a.out = reinterpret_cast<Real *>(out);
-    constexpr size_t lds = lds_bytes<T, Real, false>();
-    hipLaunchKernelGGL((id_kernel<T, Real>), dim3((n + EPB - 1) / EPB), dim3(BIOIM_EPB * T::G), lds, h->stream, a);
+/* an entry point's argument list F<void> as the kernel's F<P>: the same struct but for its pointee type */
+template <typename P, template <typename> class F> F<P> typed(const F<void> &c) {
+    static_assert(sizeof(F<P>) == sizeof(F<void>) && alignof(F<P>) == alignof(F<void>) &&
+                  std::is_standard_layout<F<P>>::value && std::is_trivially_copyable<F<P>>::value,
+                  "the argument list must differ in its pointee type only");
+    F<P> a;
+    memcpy(&a, &c, sizeof a);
+    return a;
 }
 
-template <class T, typename Real> void ma_launch_impl(bioim_handle_t *h, const MuscleEvalCall &c) {
-    constexpr int EPB = BIOIM_EPB;
-    MaArgs<T, Real> a;
-    a.Mg = reinterpret_cast<const DModel<Real> *>(h->model);
-    a.Sg = reinterpret_cast<const SModel<T, Real> *>(h->smodel);
-    a.n = c.n;
-    a.q = reinterpret_cast<const Real *>(c.q); a.u = reinterpret_cast<const Real *>(c.u);
-    a.act = reinterpret_cast<const Real *>(c.act); a.lce = reinterpret_cast<const Real *>(c.lce);
-    a.length = reinterpret_cast<Real *>(c.length); a.speed = reinterpret_cast<Real *>(c.speed);
-    a.dldq = reinterpret_cast<Real *>(c.dldq); a.fiber = reinterpret_cast<Real *>(c.fiber);
-    a.tau = reinterpret_cast<Real *>(c.tau);
-    constexpr size_t lds = lds_bytes<T, Real, false>();
-    hipLaunchKernelGGL((ma_kernel<T, Real>), dim3((c.n + EPB - 1) / EPB), dim3(BIOIM_EPB * T::G), lds, h->stream, a);
+/* Every analysis launch: n states, one per T::G lanes, EPB to a workgroup,
+ * `lds` bytes (the model image and EPB state regions) on the handle's stream;
+ * model / smodel: the DModel<Real> / SModel<T, Real> images on the device. */
+template <int EPB, class T, typename Real, typename P, template <typename> class F>
+void analysis_launch(bioim_handle_t *h, void (*kernel)(ModelArgs<T, Real>, F<P>), const F<void> &c, size_t lds,
+                     const void *model, const void *smodel) {
+    const ModelArgs<T, Real> md{static_cast<const DModel<Real> *>(model), static_cast<const SModel<T, Real> *>(smodel)};
+    hipLaunchKernelGGL(kernel, dim3((c.n + EPB - 1) / EPB), dim3(EPB * T::G), lds, h->stream, md, typed<P>(c));
 }
 
-template <class T> void so_launch_impl(bioim_handle_t *h, const StaticOptCall &c) {
-    constexpr int EPB = BIOIM_EPB;
-    using Real = double;
-    SoArgs<T, Real> a;
-    a.Mg = reinterpret_cast<const DModel<Real> *>(h->model);
-    a.Sg = reinterpret_cast<const SModel<T, Real> *>(h->smodel);
-    a.n = c.n; a.passive = c.passive;
-    a.q = reinterpret_cast<const Real *>(c.q); a.u = reinterpret_cast<const Real *>(c.u);
-    a.tau = reinterpret_cast<const Real *>(c.tau); a.row_weight = reinterpret_cast<const Real *>(c.row_weight);
-    a.lo = c.lo; a.hi = c.hi;
-    a.act = reinterpret_cast<Real *>(c.act); a.residual = reinterpret_cast<Real *>(c.residual);
-    a.tau_muscle = reinterpret_cast<Real *>(c.tau_muscle); a.capacity = reinterpret_cast<Real *>(c.capacity);
-    a.status = c.status;
-    constexpr size_t lds = lds_bytes<T, Real, false>();
-    hipLaunchKernelGGL((so_kernel<T, Real>), dim3((c.n + EPB - 1) / EPB), dim3(BIOIM_EPB * T::G), lds, h->stream, a);
+template <class T, typename Real> void id_launch_impl(bioim_handle_t *h, const IdFields<void> &c) {
+    analysis_launch<BIOIM_EPB>(h, &id_kernel<T, Real>, c, lds_bytes<T, Real, false>(), h->model, h->smodel);
 }
 
-template <class T> void ik_launch_impl(bioim_handle_t *h, const IkCall &c) {
-    constexpr int EPB = BIOIM_EPB;
-    using Real = double;
-    IkArgs<T, Real> a;
-    a.Mg = reinterpret_cast<const DModel<Real> *>(h->model);
-    a.Sg = reinterpret_cast<const SModel<T, Real> *>(h->smodel);
-    a.n = c.n; a.nm = c.nm; a.max_iter = c.max_iter;
-    a.marker_body = c.marker_body;
-    a.marker_loc = reinterpret_cast<const Real *>(c.marker_loc); a.weight = reinterpret_cast<const Real *>(c.weight);
-    a.x_exp = reinterpret_cast<const Real *>(c.x_exp); a.q0 = reinterpret_cast<const Real *>(c.q0);
-    a.coord_weight = reinterpret_cast<const Real *>(c.coord_weight);
-    a.q_target = reinterpret_cast<const Real *>(c.q_target);
-    a.tol = c.tol;
-    a.q = reinterpret_cast<Real *>(c.q); a.markers = reinterpret_cast<Real *>(c.markers);
-    a.err = reinterpret_cast<Real *>(c.err); a.jacobian = reinterpret_cast<Real *>(c.jacobian);
-    a.status = c.status;
-    constexpr size_t lds = lds_bytes<T, Real, false>();
-    hipLaunchKernelGGL((ik_kernel<T, Real>), dim3((c.n + EPB - 1) / EPB), dim3(BIOIM_EPB * T::G), lds, h->stream, a);
+template <class T, typename Real> void ma_launch_impl(bioim_handle_t *h, const MaFields<void> &c) {
+    analysis_launch<BIOIM_EPB>(h, &ma_kernel<T, Real>, c, lds_bytes<T, Real, false>(), h->model, h->smodel);
+}
+
+template <class T> void so_launch_impl(bioim_handle_t *h, const SoFields<void> &c) {
+    analysis_launch<BIOIM_EPB>(h, &so_kernel<T, double>, c, lds_bytes<T, double, false>(), h->model, h->smodel);
+}
+
+template <class T> void ik_launch_impl(bioim_handle_t *h, const IkFields<void> &c) {
+    analysis_launch<BIOIM_EPB>(h, &ik_kernel<T, double>, c, lds_bytes<T, double, false>(), h->model, h->smodel);
+}
+
+/* its own LDS size (IaLay: the env regions plus the private tails) and states per workgroup */
+template <class T> void ia_launch_impl(bioim_handle_t *h, const IaFields<void> &c) {
+    using IA = IaLay<T, double>;
+    analysis_launch<IA::EPB>(h, &ia_kernel<T, double>, c, IA::lds_bytes, h->model, h->smodel);
 }
 
 /* fp32 handles: the fp64 DModel / SModel of jr_kernel, built from the pack
@@ -6586,81 +6436,37 @@ template <class T> int jr_fp64_model(bioim_handle_t *h) {
 
 /* IO: the handle's precision (the caller's arrays); the kernel is fp64 either
  * way, on the handle's own image (fp64 handle) or on its fp64 copy (fp32) */
-template <class T, typename IO> int jr_launch_impl(bioim_handle_t *h, const JrCall &c) {
-    constexpr int EPB = BIOIM_EPB;
+template <class T, typename IO> int jr_launch_impl(bioim_handle_t *h, const JrFields<void> &c) {
     constexpr bool own = std::is_same<IO, double>::value;
     if constexpr (!own) {
         if (const int rc = jr_fp64_model<T>(h)) return rc;
     }
-    JrArgs<T, IO> a;
-    a.Mg = reinterpret_cast<const DModel<double> *>(own ? h->model : h->jr_model);
-    a.Sg = reinterpret_cast<const SModel<T, double> *>(own ? h->smodel : h->jr_smodel);
-    a.n = c.n; a.flags = c.flags; a.frame = c.frame;
-    a.q = reinterpret_cast<const IO *>(c.q); a.u = reinterpret_cast<const IO *>(c.u);
-    a.qdd = reinterpret_cast<const IO *>(c.qdd); a.ft = reinterpret_cast<const IO *>(c.ft);
-    a.ext = reinterpret_cast<const IO *>(c.ext);
-    a.reaction = reinterpret_cast<IO *>(c.reaction); a.point = reinterpret_cast<IO *>(c.point);
-    a.tau_joint = reinterpret_cast<IO *>(c.tau_joint); a.muscle_wrench = reinterpret_cast<IO *>(c.muscle_wrench);
-    constexpr size_t lds = lds_bytes<T, double, false>();
-    hipLaunchKernelGGL((jr_kernel<T, IO>), dim3((c.n + EPB - 1) / EPB), dim3(BIOIM_EPB * T::G), lds, h->stream, a);
+    analysis_launch<BIOIM_EPB>(h, &jr_kernel<T, IO>, c, lds_bytes<T, double, false>(), own ? h->model : h->jr_model,
+                               own ? h->smodel : h->jr_smodel);
     return 0;
 }
 
-/* its own LDS size (IaLay: the env regions plus the private tails) and states per workgroup */
-template <class T> void ia_launch_impl(bioim_handle_t *h, const IaCall &c) {
-    using Real = double;
-    constexpr int EPB = IaLay<T, Real>::EPB;
-    IaArgs<T, Real> a;
-    a.Mg = reinterpret_cast<const DModel<Real> *>(h->model);
-    a.Sg = reinterpret_cast<const SModel<T, Real> *>(h->smodel);
-    a.n = c.n; a.kind = c.kind; a.thr = c.force_threshold;
-    a.q = reinterpret_cast<const Real *>(c.q); a.u = reinterpret_cast<const Real *>(c.u);
-    a.ft = reinterpret_cast<const Real *>(c.ft); a.tau_act = reinterpret_cast<const Real *>(c.tau_act);
-    a.ext = reinterpret_cast<const Real *>(c.ext); a.cpoint = reinterpret_cast<const Real *>(c.cpoint);
-    a.cactive = c.cactive;
-    a.accel = reinterpret_cast<Real *>(c.accel); a.com_accel = reinterpret_cast<Real *>(c.com_accel);
-    a.reaction = reinterpret_cast<Real *>(c.reaction); a.cpoint_out = reinterpret_cast<Real *>(c.cpoint_out);
-    a.cactive_out = c.cactive_out; a.status = c.status;
-    constexpr size_t lds = IaLay<T, Real>::lds_bytes;
-    hipLaunchKernelGGL((ia_kernel<T, Real>), dim3((c.n + EPB - 1) / EPB), dim3(EPB * T::G), lds, h->stream, a);
-}
+/* the dynamic LDS kernel K (in parentheses) may ask for, above the 64 KiB default; a failure names the kernel */
+#define ALLOW_LDS(K, BYTES) \
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BYTES)))
 
 template <class T, typename Real> int upload_smodel(bioim_handle_t *h) {
     static_assert(lds_bytes<T, Real, true>() <= 163840, "LDS image + env regions exceed 160 KiB");
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&env_kernel<T, Real, false, false>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, Real, false>()));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&env_kernel<T, Real, true, false>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, Real, true>()));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&env_kernel<T, Real, false, true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, Real, false>()));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&env_kernel<T, Real, true, true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, Real, true>()));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&env_kernel<T, Real, false, false, true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, Real, false>()));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&env_kernel<T, Real, true, false, true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, Real, true>()));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&env_kernel<T, Real, false, true, true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, Real, false>()));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&env_kernel<T, Real, true, true, true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, Real, true>()));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&id_kernel<T, Real>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, Real, false>()));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&rollout_kernel<T, Real>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, Real, false>()));
-    if constexpr (T::NM > 0)
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&ma_kernel<T, Real>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, Real, false>()));
-    if constexpr (T::NM > 0 && std::is_same<Real, double>::value)
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&so_kernel<T, double>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, double, false>()));
-    if constexpr (std::is_same<Real, double>::value)
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&ik_kernel<T, double>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, double, false>()));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&jr_kernel<T, Real>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes<T, double, false>()));
-    if constexpr (std::is_same<Real, double>::value)
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&ia_kernel<T, double>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)IaLay<T, double>::lds_bytes));
+    ALLOW_LDS((env_kernel<T, Real, false, false>), (lds_bytes<T, Real, false>()));
+    ALLOW_LDS((env_kernel<T, Real, true, false>), (lds_bytes<T, Real, true>()));
+    ALLOW_LDS((env_kernel<T, Real, false, true>), (lds_bytes<T, Real, false>()));
+    ALLOW_LDS((env_kernel<T, Real, true, true>), (lds_bytes<T, Real, true>()));
+    ALLOW_LDS((env_kernel<T, Real, false, false, true>), (lds_bytes<T, Real, false>()));
+    ALLOW_LDS((env_kernel<T, Real, true, false, true>), (lds_bytes<T, Real, true>()));
+    ALLOW_LDS((env_kernel<T, Real, false, true, true>), (lds_bytes<T, Real, false>()));
+    ALLOW_LDS((env_kernel<T, Real, true, true, true>), (lds_bytes<T, Real, true>()));
+    ALLOW_LDS((id_kernel<T, Real>), (lds_bytes<T, Real, false>()));
+    ALLOW_LDS((rollout_kernel<T, Real>), (lds_bytes<T, Real, false>()));
+    if constexpr (T::NM > 0) ALLOW_LDS((ma_kernel<T, Real>), (lds_bytes<T, Real, false>()));
+    if constexpr (T::NM > 0 && std::is_same<Real, double>::value) ALLOW_LDS((so_kernel<T, double>), (lds_bytes<T, double, false>()));
+    if constexpr (std::is_same<Real, double>::value) ALLOW_LDS((ik_kernel<T, double>), (lds_bytes<T, double, false>()));
+    ALLOW_LDS((jr_kernel<T, Real>), (lds_bytes<T, double, false>()));
+    if constexpr (std::is_same<Real, double>::value) ALLOW_LDS((ia_kernel<T, double>), (IaLay<T, double>::lds_bytes));
     constexpr size_t B = smodel_bytes<T, Real>();
     std::vector<unsigned char> img(B, 0);
     build_smodel<T, Real>(h->pack, *reinterpret_cast<SModel<T, Real> *>(img.data()));
@@ -7374,7 +7180,8 @@ int bioim_id_eval(bioim_handle_t *h, int op, int n, const void *q, const void *u
     if (n > 0 && ((use_u && !u) || (use_v && !v))) return fail(BIOIM_E_ARG, "bioim_id_eval: missing u or v");
     if (n == 0) return 0;
     HIPCHK(hipSetDevice(h->device));
-    h->ops.id_launch(h, op, n, q, u, v, out);
+    const IdFields<void> c{n, op, q, u, v, out};
+    h->ops.id_launch(h, c);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -7389,7 +7196,7 @@ int bioim_muscle_eval(bioim_handle_t *h, int n, const void *q, const void *u, co
     if (h->nmuscle <= 0 || !h->ops.ma_launch) return fail(BIOIM_E_ARG, "bioim_muscle_eval: the model has no muscles");
     if (n == 0) return 0;
     HIPCHK(hipSetDevice(h->device));
-    const MuscleEvalCall c{n, q, u, act, lce, length, speed, dldq, fiber, tau};
+    const MaFields<void> c{n, q, u, act, lce, length, speed, dldq, fiber, tau};
     h->ops.ma_launch(h, c);
     HIPCHK(hipGetLastError());
     return 0;
@@ -7409,7 +7216,7 @@ int bioim_static_opt(bioim_handle_t *h, int n, const void *q, const void *u, con
     if (h->precision != 64 || !h->ops.so_launch) return fail(BIOIM_E_ARG, "bioim_static_opt: fp64 handles only");
     if (n == 0) return 0;
     HIPCHK(hipSetDevice(h->device));
-    const StaticOptCall c{n, q, u, tau, row_weight, lo, hi, passive, act, residual, tau_muscle, capacity, status};
+    const SoFields<void> c{n, passive, q, u, tau, row_weight, lo, hi, act, residual, tau_muscle, capacity, status};
     h->ops.so_launch(h, c);
     HIPCHK(hipGetLastError());
     return 0;
@@ -7434,8 +7241,8 @@ int bioim_ik_solve(bioim_handle_t *h, int n, int nm, const int32_t *marker_body,
     if (h->precision != 64 || !h->ops.ik_launch) return fail(BIOIM_E_ARG, "bioim_ik_solve: fp64 handles only");
     if (n == 0) return 0;
     HIPCHK(hipSetDevice(h->device));
-    const IkCall c{n, nm, marker_body, marker_loc, weight, x_exp, q0, coord_weight, q_target, tol, max_iter,
-                   q, markers, err, jacobian, status};
+    const IkFields<void> c{n, nm, max_iter, marker_body, marker_loc, weight, x_exp, q0, coord_weight, q_target, tol,
+                           q, markers, err, jacobian, status};
     h->ops.ik_launch(h, c);
     HIPCHK(hipGetLastError());
     return 0;
@@ -7455,7 +7262,7 @@ int bioim_joint_reaction(bioim_handle_t *h, int n, const void *q, const void *u,
         return fail(BIOIM_E_ARG, "bioim_joint_reaction: no output requested");
     if (n == 0) return 0;
     HIPCHK(hipSetDevice(h->device));
-    const JrCall c{n, q, u, qdd, ft, ext, flags, frame, reaction, point, tau_joint, muscle_wrench};
+    const JrFields<void> c{n, flags, frame, q, u, qdd, ft, ext, reaction, point, tau_joint, muscle_wrench};
     if (const int rc = h->ops.jr_launch(h, c)) return rc;
     HIPCHK(hipGetLastError());
     return 0;
@@ -7480,8 +7287,8 @@ int bioim_induced_accel(bioim_handle_t *h, int n, const void *q, const void *u, 
     if (h->precision != 64 || !h->ops.ia_launch) return fail(BIOIM_E_ARG, "bioim_induced_accel: fp64 handles only");
     if (n == 0) return 0;
     HIPCHK(hipSetDevice(h->device));
-    const IaCall c{n, q, u, ft, tau_act, ext, kind, cactive, cpoint, force_threshold,
-                   accel, com_accel, reaction, cpoint_out, cactive_out, status};
+    const IaFields<void> c{n, kind, force_threshold, q, u, ft, tau_act, ext, cpoint, cactive,
+                           accel, com_accel, reaction, cpoint_out, cactive_out, status};
     h->ops.ia_launch(h, c);
     HIPCHK(hipGetLastError());
     return 0;
