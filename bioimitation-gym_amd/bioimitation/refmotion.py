@@ -160,3 +160,154 @@ def load_reference_tables(ref_dir, coord_order, dt=0.01):
         for a, ax in enumerate('XYZ'):
             x[:, k, a] = xd[f'{b}_{ax}'].to_numpy()[:n]
     return dict(time=qd['time'].to_numpy()[:n], q=q, u=u, x=x)
+
+
+# ------------------------------------------------- run-time reference motions
+MAX_ROWS_TEXT = 'a clip may be 3 to {hi} rows after resampling at {dt} s: {lo_s:.2f} s to {hi_s:.2f} s'
+
+
+class ReferenceMotion:
+    """A reference motion in the form the packs carry: ``time`` [rows] (a
+    0.01 s grid from 0), ``q`` / ``u`` [rows][ncoord] in CoordinateSet order
+    (radians and metres), ``x`` [rows][len(REF_BODIES)][3] the mass centres of
+    REF_BODIES in ground.  ``config={'reference': ref}`` gives it to an env
+    (``registry.load_pack``).  ``kinematics``: the body kinematics the tables
+    were made from ({'bodies', 'com', 'orient', 'system'} as arrays), which
+    ``save`` writes in full."""
+
+    def __init__(self, env_id, time, q, u, x, coords, kinematics=None):
+        self.env_id, self.coords = env_id, list(coords)
+        self.time, self.q, self.u, self.x = (np.asarray(a, dtype=np.float64) for a in (time, q, u, x))
+        self.kinematics = kinematics
+
+    def save(self, path):
+        """The four storages the envs read, into the directory ``path``:
+        ``task_Kinematics_{q,u}.sto`` and
+        ``task_BodyKinematics_{pos,vel}_global.sto`` (with the kinematics the
+        tables were made from: every body's columns, and ``_acc_`` too; without
+        them: the REF_BODIES position columns only, and no velocity file)."""
+        os.makedirs(path, exist_ok=True)
+        write_sto(os.path.join(path, 'task_Kinematics_q.sto'), ['time'] + self.coords,
+                  np.column_stack([self.time, self.q]), name='Coordinates')
+        write_sto(os.path.join(path, 'task_Kinematics_u.sto'), ['time'] + self.coords,
+                  np.column_stack([self.time, self.u]), name='Speeds')
+        if self.kinematics is not None:
+            from .body_kinematics import write_sto as write_bk
+            write_bk(path, self.time, self.kinematics, bodies=self.kinematics['bodies'], local=False)
+        else:
+            labs = ['time'] + [f'{b}_{ax}' for b in REF_BODIES for ax in 'XYZ']
+            write_sto(os.path.join(path, 'task_BodyKinematics_pos_global.sto'), labs,
+                      np.column_stack([self.time, self.x.reshape(self.x.shape[0], -1)]), name='BodyKinematics')
+        return path
+
+
+def sphere_points(pk, bodies):
+    """The pack's contact spheres as ``BodyKinematics`` points, [(OpenSim body
+    name, centre in that body's frame)], and their radii."""
+    pts, radii = [], []
+    for s in range(pk.nsphere):
+        sp = pk.sphere[s]
+        ob = pk.osbody[sp.obody]
+        R, p = np.array(ob.R).reshape(3, 3), np.array(ob.p)
+        pts.append((bodies[sp.obody], tuple(R.T @ (np.array(sp.loc) - p))))
+        radii.append(float(sp.radius))
+    return pts, np.array(radii)
+
+
+def deepest_penetration(bk, pk, q_dof):
+    """max over the rows and the pack's contact spheres of radius - centre
+    height: how far the lowest sphere reaches below the ground plane (one
+    ``BodyKinematics.eval`` launch with the spheres as points)."""
+    pts, radii = sphere_points(pk, bk.bodies)
+    y = bk.eval(q_dof, points=pts, want=('point',))['point'][:, :, 0, 1].cpu().numpy()
+    return float((radii[None, :] - y).max())
+
+
+def reference_from_coordinates(env_id, time, q, lowpass_hz=6.0, penetration=0.01, rebase_tx=True, device=0):
+    """``synthesize_reference``'s recipe from coordinates alone, without the
+    ``.osim``: a ``ReferenceMotion`` for ``env_id`` from ``q`` [rows][ncoord]
+    (the pack's coordinate order, radians and metres: what
+    ``InverseKinematics.solve_trc`` returns) sampled at ``time`` [rows].
+
+    Resampled linearly at 0.01 s (the grid then starts at 0: an env reads row
+    ``istep``); the zero-phase Butterworth low-pass at ``lowpass_hz`` (None: no
+    filter); locked coordinates held at the pack's default value, speed 0;
+    pelvis_ty shifted so that the deepest contact-sphere penetration over the
+    clip is ``penetration`` (None: no shift) and, with ``rebase_tx``, pelvis_tx
+    starting at 0; u from the cubic-spline derivative.  The spheres' heights and
+    the bodies' mass centres (``x``) come from ``BodyKinematics`` on ``device``:
+    one launch each over all rows."""
+    from .body_kinematics import BodyKinematics
+    from .obslayout import load_names
+    from .packdef import MAX_REFROWS
+    from .registry import load_pack
+    pk, dt = load_pack(env_id), 0.01
+    coords = list(load_names(env_id)['coords'])
+    time, q = np.asarray(time, dtype=np.float64), np.asarray(q, dtype=np.float64)
+    if time.ndim != 1 or q.ndim != 2 or q.shape != (time.size, pk.ncoord):
+        raise ValueError(f'reference_from_coordinates: time must have shape (rows,) and q (rows, {pk.ncoord}) in the '
+                         f'order {coords}; got {time.shape} and {q.shape}')
+    if time.size < 2 or not np.all(np.isfinite(time)) or not np.all(np.diff(time) > 0):
+        raise ValueError('reference_from_coordinates: time must be finite and strictly increasing (two rows or more)')
+    if not np.all(np.isfinite(q)):
+        raise ValueError('reference_from_coordinates: q has non-finite entries')
+    t, q = resample_linear(time, q, dt)
+    if not 3 <= t.size <= MAX_REFROWS:
+        raise ValueError(f'reference_from_coordinates: {t.size} rows; ' + MAX_ROWS_TEXT.format(
+            hi=MAX_REFROWS, dt=dt, lo_s=2 * dt, hi_s=(MAX_REFROWS - 1) * dt))
+    t = dt * np.arange(t.size, dtype=np.float64)
+    if lowpass_hz is not None:
+        q = _lowpass(q, dt, float(lowpass_hz))
+    locked = [c for c in range(pk.ncoord) if pk.coord[c].dof < 0]
+    free = [c for c in range(pk.ncoord) if pk.coord[c].dof >= 0]
+    dof_of = [int(pk.coord[c].dof) for c in free]
+    for c in locked:
+        q[:, c] = pk.coord[c].default_value
+
+    def dofs(a):
+        out = np.zeros((a.shape[0], pk.ndof))
+        out[:, dof_of] = a[:, free]
+        return out
+    bk = BodyKinematics(env_id, device=device)
+    try:
+        if penetration is not None:
+            if pk.coord_ty < 0 or pk.nsphere == 0:
+                raise ValueError(f'reference_from_coordinates: {env_id} has no pelvis_ty or no contact spheres to '
+                                 'calibrate the ground with; pass penetration=None')
+            q[:, pk.coord_ty] += deepest_penetration(bk, pk, dofs(q)) - float(penetration)
+        if rebase_tx and pk.coord_tx >= 0:
+            q[:, pk.coord_tx] -= q[0, pk.coord_tx]
+        u = _spline_derivative(t, q)
+        for c in locked:
+            u[:, c] = 0.0
+        out = bk.eval(dofs(q), dofs(u), dofs(_spline_derivative(t, u)), want=('com', 'orient', 'system'))
+        kin = {k: v.cpu().numpy() for k, v in out.items()}
+        kin['bodies'] = list(bk.bodies)
+    finally:
+        bk.close()
+    x = np.zeros((t.size, len(REF_BODIES), 3))
+    for k in range(len(REF_BODIES)):
+        b = int(pk.rw_body[k])
+        x[:, k] = kin['com'][:, b, 0, :] if b >= 0 else kin['system'][:, 0, :]
+    return ReferenceMotion(env_id, t, q, u, x, coords, kinematics=kin)
+
+
+def reference_tables(ref, coords, dt=0.01):
+    """``config['reference']`` as a dict of arrays time, q, u, x: a
+    ``ReferenceMotion``, a dict with those keys, or a directory holding the
+    four storages (read with ``load_reference_tables`` and the pack's
+    coordinate names ``coords``)."""
+    if isinstance(ref, (str, os.PathLike)):
+        if not os.path.isdir(ref):
+            raise ValueError(f"config['reference']: {os.fspath(ref)!r} is not a directory (it must hold "
+                             'task_Kinematics_{q,u}.sto and task_BodyKinematics_pos_global.sto)')
+        return load_reference_tables(os.fspath(ref), list(coords), dt)
+    if isinstance(ref, dict):
+        missing = [k for k in ('time', 'q', 'u', 'x') if k not in ref]
+        if missing:
+            raise ValueError(f"config['reference']: the dict lacks {missing} (it needs time, q, u, x)")
+        return {k: ref[k] for k in ('time', 'q', 'u', 'x')}
+    if all(hasattr(ref, k) for k in ('time', 'q', 'u', 'x')):
+        return dict(time=ref.time, q=ref.q, u=ref.u, x=ref.x)
+    raise ValueError("config['reference'] must be a ReferenceMotion, a dict with time, q, u, x, or a directory with "
+                     f'the four reference storages; got {type(ref).__name__}')

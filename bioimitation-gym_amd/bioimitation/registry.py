@@ -203,9 +203,68 @@ def _pack_path(env_id: str) -> str:
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), 'data', 'packs', env_id + '.npz')
 
 
+def apply_cycle(pk, env_id: str, cycle):
+    """``config['cycle']`` (an int >= 1) replaces the recipe's gait cycle length
+    (the period of the phase observation): the one env parameter that goes with
+    a clip and cannot be read off its tables."""
+    if isinstance(cycle, bool) or isinstance(cycle, str) or int(cycle) != cycle or int(cycle) < 1:
+        raise ValueError(f"{env_id}: config['cycle'] must be an integer >= 1, got {cycle!r}")
+    pk.cycle = int(cycle)
+
+
+def apply_reference(pk, env_id: str, ref):
+    """Replace ``pk``'s reference motion by the user's (``config['reference']``:
+    a ``refmotion.ReferenceMotion``, a dict with time, q, u, x, or a directory
+    holding the four storages) and recompute the episode by the recipe's own
+    rule.  The tables are written as ``modelpack.compile_pack`` writes them
+    (nrows, ref_time, ref_istep, ref_q, ref_u, ref_x; rows past nrows zero).
+    ``n_episode`` is rows - 2 where the recipe says 'rows-2', else the recipe's
+    integer capped at rows - 2; ``reset_hi`` is N // 2 where it says 'N/2', else
+    its integer capped at N."""
+    import numpy as np
+    from . import packdef as P
+    from .obslayout import load_names
+    from .refmotion import MAX_ROWS_TEXT, reference_tables
+    what = f"{env_id}: config['reference']"
+    tabs = reference_tables(ref, load_names(env_id)['coords'], pk.step_size)
+    try:
+        t, q, u, x = (np.array(tabs[k], dtype=np.float64) for k in ('time', 'q', 'u', 'x'))
+    except (TypeError, ValueError):
+        raise ValueError(f'{what}: time, q, u and x must hold real numbers') from None
+    rows = t.shape[0] if t.ndim == 1 else -1
+    if rows < 0 or q.shape != (rows, pk.ncoord) or u.shape != (rows, pk.ncoord) or x.shape != (rows, P.NREFBODY, 3):
+        raise ValueError(f'{what}: time must have shape (rows,), q and u (rows, {pk.ncoord}), x (rows, {P.NREFBODY}, 3); '
+                         f'got {t.shape}, {q.shape}, {u.shape}, {x.shape}')
+    if not 3 <= rows <= P.MAX_REFROWS:
+        raise ValueError(f'{what}: {rows} rows; ' + MAX_ROWS_TEXT.format(
+            hi=P.MAX_REFROWS, dt=pk.step_size, lo_s=2 * pk.step_size, hi_s=(P.MAX_REFROWS - 1) * pk.step_size))
+    if not all(np.all(np.isfinite(a)) for a in (t, q, u, x)):
+        raise ValueError(f'{what}: non-finite entries')
+    # an env reads row istep of the tables, so row r is time r * step_size (storages carry 10 decimals)
+    if np.abs(t - pk.step_size * np.arange(rows)).max() > 1e-8:
+        raise ValueError(f'{what}: the time column must be the uniform grid 0, {pk.step_size}, {2 * pk.step_size}, ... '
+                         f'(refmotion.reference_from_coordinates resamples a clip to it)')
+    pk.nrows = rows
+    for name, tab in (('ref_q', q), ('ref_u', u), ('ref_x', x)):
+        view = np.ctypeslib.as_array(getattr(pk, name))
+        view[...] = 0.0
+        view[:rows, :tab.shape[1]] = tab
+    for r in range(P.MAX_REFROWS):
+        pk.ref_time[r] = float(t[r]) if r < rows else 0.0
+        # compile_pack's rule, literal 0.01 and float64 truncation included (opensim_wrapper.py:306): 0.29 / 0.01
+        # truncates to 28, so a reset at such a row starts one step early, on a run-time clip as on the packaged
+        # ones.  Kept, not mended to istep = r: a pack given its own tables stays byte for byte what it is, and
+        # the oracle and the golden episodes reset the same way.
+        pk.ref_istep[r] = int(float(t[r]) / 0.01) if r < rows else 0
+    spec = RECIPES[env_id]['spec']
+    pk.n_episode = rows - 2 if spec['n_episode'] == 'rows-2' else min(int(spec['n_episode']), rows - 2)
+    pk.reset_hi = pk.n_episode // 2 if spec['reset_hi'] == 'N/2' else min(int(spec['reset_hi']), pk.n_episode)
+
+
 def load_pack(env_id: str, config: dict = None):
     """The committed ModelPack of ``env_id`` with the user's env config
-    applied (reward weights, horizon, obs switches, test mode)."""
+    applied (reward weights, horizon, obs switches, a run-time reference
+    motion, test mode)."""
     import numpy as np
     from . import packdef as P
     from .modelpack import pack_from_bytes
@@ -232,6 +291,10 @@ def load_pack(env_id: str, config: dict = None):
     n += 3 * pk.n_obs_bpos + 3 * pk.n_obs_bvel + 3 * pk.nmuscle
     n += 6 * pk.ncforce if spec.use_grf else 0
     pk.obs_dim = n
+    if 'reference' in cfg:
+        apply_reference(pk, env_id, cfg['reference'])
+    if cfg.get('cycle') is not None:
+        apply_cycle(pk, env_id, cfg['cycle'])
     if cfg.get('mode') == 'test':
         pk.n_episode = pk.nrows - 2   # muscle_walking_imitation_env2D.py:74-75
         pk.reset_hi = 0               # reset index 0 in test mode (:141-142)

@@ -677,6 +677,42 @@ class VectorEnv:
         (res.contributors, res.coords), res.kind = self._ia_names, kind
         return res
 
+    def body_kinematics(self, env_ids=None, qdd=None, points=None, local=False, want=('com', 'system'), rows=None):
+        """Body and point kinematics (``bioimitation.body_kinematics``) at the
+        envs' own state: {key: device tensor} for the keys of ``want``, one
+        row per env (or per listed env, in the list's order; distinct ids).
+        q and u are gathered on the device (``state_rows``), then one
+        ``bioim_body_kin`` launch on the env's own handle and stream: no host
+        round trip and no synchronization (ids given as a list or array are
+        checked on the host).  ``qdd``: None (zeros: the accelerations are then
+        the velocity terms alone), ``[n][ndof]`` accelerations of the caller's,
+        or 'own': the envs' forward-dynamics q'' from a REALIZE report, as
+        ``joint_reaction`` takes them.  ``points``: [(body name or 'ground',
+        (x, y, z))].  A read: the env state, the next steps' outputs and the
+        realize cache stay what they are.  ``rows``: state rows already
+        gathered for these envs."""
+        from . import body_kinematics as bk
+        pk = self.pack
+        if getattr(self, '_bk_bodies', None) is None:
+            from .obslayout import load_names
+            self._bk_bodies = list(load_names(self.env_id)['bodies'])
+        n, q, u, realize = self._own_state_inputs(env_ids, rows)
+        own = isinstance(qdd, str)
+        if own and qdd != 'own':
+            raise ValueError(f"body kinematics: qdd must be None, 'own' or [n][ndof] accelerations, got {qdd!r}")
+        _, want, pt_body, pt_local = bk.check_args(pk.ndof, self._bk_bodies, q, u, None if own else qdd, points, local,
+                                                   want)
+        if q.shape[0] != n:
+            raise ValueError(f'body_kinematics: rows has {q.shape[0]} rows for {n} envs')
+        if own:
+            qdd = realize()['qdd'] if n else None
+        elif qdd is not None:
+            from ._analysis import to_device
+            qdd = to_device(qdd, self.device, self.dtype)
+        res = bk.Result(bk.launch(self, q, u, qdd, pt_body, pt_local, local, want))
+        res.bodies, res.local = self._bk_bodies, bool(local)
+        return res
+
     def load_state(self, rows, env_ids=None):
         """Write flat state rows (``state_rows``' layout: a contiguous
         (n, state_dim) float64 tensor on the env's device) into the listed
@@ -819,6 +855,9 @@ class MixedVectorEnv:
 
     def __init__(self, segments, config=None, device: int = 0, precision: int = 64, seed: int = 0,
                  auto_reset: bool = False, env_offset: int = 0):
+        if 'reference' in (config or {}):
+            raise ValueError("MixedVectorEnv: config['reference'] holds one model's reference motion (its coordinates "
+                             'and bodies); a mixed batch takes no run-time reference')
         import torch
         self.envs, off = [], 0
         for env_id, n in segments:

@@ -4512,6 +4512,226 @@ DEV void osim_report(const DModel<Real> &M, const SModel<T, Real> &SM, const Rea
     if (lane < T::NL) out[OLIM + lane] = lds[LY::LIM + 4 * lane];
 }
 
+/* ---------------------------------------------------------- body kinematics
+ * bioim_body_kin (include/bioim.h): OpenSim's BodyKinematics and
+ * PointKinematics at n arbitrary (q, u, q'') rows, plus the whole-body mass
+ * centre, momentum and energy.  ma_kernel's launch shape and prologue (one
+ * state per G lanes, the model image in LDS, the step's kinematics).  Then:
+ *   1. body lane c: the full spatial acceleration, AL_c + sum over the dofs d
+ *      on c's root path of S_d q''_d (osim_report's body_acc), in place in AL;
+ *   2. the stations — every OpenSim body's origin, every OpenSim body's own
+ *      mass centre, the caller's points — are one list that the lanes walk in
+ *      strides of G through one piece of code (bk_station), so a point at a
+ *      body's origin or mass centre is that row bit for bit;
+ *   3. the lanes walk the OpenSim bodies again for the angles and R;
+ *   4. body lane c leaves its mass centre's p, v, a, its kinetic energy and
+ *      I_c w_c in the (otherwise unused) IC / WB slots, and lane 0 sums them
+ *      over c = 0 .. NB-1, so a state's sums do not depend on its neighbours.
+ * The point table and the OpenSim bodies' mass centres are part of the
+ * argument list itself (the entry point checks and copies them): the lanes
+ * read them from the kernel-argument segment.  No atomics, nothing of the env
+ * state is read or written, no workgroup barrier after the exit. */
+template <typename P> struct BkFields {   /* bioim_body_kin */
+    int n, npt, flags, pad;
+    const P *q, *u, *qdd;
+    P *origin, *com, *orient, *rot, *system, *momentum, *energy, *point;
+    double os_com[BIOIM_MAX_OSBODY][3];             /* each OpenSim body's mass centre, in its own frame */
+    double pt_local[BIOIM_BK_MAX_POINTS][3];
+    int8_t pt_body[BIOIM_BK_MAX_POINTS];            /* OpenSim body index, -1: ground */
+};
+
+/* A station `loc` of the OpenSim body placed at (osR, osp) in its composite
+ * body: position (from the shifted ground origin), velocity and acceleration
+ * in ground.  kb: the composite body's frame (R9 o3 w3 vO3); ab: its spatial
+ * acceleration (alpha3, aO3), the q'' terms included. */
+template <typename Real>
+DEV void bk_station(const Real *kb, const Real *ab, const Real *osR, const Real *osp, const Real *loc, Real *P, Real *v,
+                    Real *acc) {
+    Real lc[3], t[3], t2[3];
+    mv3(osR, loc, lc);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) lc[i] += osp[i];
+    mv3(kb, lc, P);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) P[i] += kb[9 + i];
+    cross3(kb + 12, P, t);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) v[i] = kb[15 + i] + t[i];
+    cross3(ab, P, t);
+    cross3(kb + 12, v, t2);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) acc[i] = ab[3 + i] + t[i] + t2[i];
+}
+
+/* o = R^T v */
+template <typename Real> DEV void bk_tmv3(const Real *R, const Real *v, Real *o) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o[i] = R[i] * v[0] + R[3 + i] * v[1] + R[6 + i] * v[2];
+}
+
+template <class T, typename Real>
+__global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_eu(1, 1))) void bk_kernel(ModelArgs<T, Real> md, BkFields<Real> a) {
+    using LY = Lay<T, Real>;
+    constexpr int G = T::G, ND = LY::ND, NB = T::NB, NOS = T::NOS, EPB = BIOIM_EPB;
+    constexpr size_t SMB = smodel_bytes<T, Real>();
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const SModel<T, Real> &SM = stage_model<EPB, T, Real>(md.Sg, smem_raw);
+    const DModel<Real> &M = *md.Mg;
+    const int lane = threadIdx.x % G, slot = threadIdx.x / G;
+    const int idx = blockIdx.x * EPB + slot;
+    if (idx >= a.n) return;
+    Real *lds = reinterpret_cast<Real *>(smem_raw + SMB) + slot * LY::SIZE;
+    const bool local = (a.flags & BIOIM_BK_LOCAL) != 0;
+    Real qd = 0, ud = 0, ad = 0;
+    if (lane < ND) {
+        qd = GAT(a.q, (size_t)idx * ND + lane, (size_t)a.n * ND);
+        ud = opt_row<Real, ND>(a.u, idx, lane, a.n);
+        ad = opt_row<Real, ND>(a.qdd, idx, lane, a.n);
+    }
+    const Real x0 = state_kinematics<BfSwitch<T>::FN, T, Real>(M, SM, lds, lane, qd, ud);
+    if (lane < ND) lds[LY::RHS + lane] = ad;
+    wave_sync();   /* frames, velocity-product accelerations, columns and q'' are out */
+    if (lane < NB) {
+        Real *ab = lds + LY::AL + 6 * lane;
+        const uint32_t dm = SM.dofmask[lane];
+        Real sa[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) sa[i] = ab[i];
+#pragma unroll
+        for (int d = 0; d < ND; ++d) {
+            const Real qdd = ((dm >> d) & 1u) ? lds[LY::RHS + d] : Real(0);
+            const Real *S = lds + LY::S + 6 * d;
+#pragma unroll
+            for (int i = 0; i < 6; ++i) sa[i] += S[i] * qdd;
+        }
+#pragma unroll
+        for (int i = 0; i < 6; ++i) ab[i] = sa[i];   /* its own slot only: no other lane reads it before the sync */
+    }
+    wave_sync();
+    /* the stations: [0, NOS) body origins, [NOS, 2 NOS) the bodies' own mass centres, then the points */
+    const int nst = 2 * NOS + a.npt;
+    for (int s = lane; s < nst; s += G) {
+        const int kind = s < NOS ? 0 : (s < 2 * NOS ? 1 : 2);
+        const int k = s - kind * NOS;
+        Real *out = kind == 0 ? a.origin : (kind == 1 ? a.com : a.point);
+        if (!out) continue;
+        const int b = kind == 2 ? (int)a.pt_body[k] : k;
+        Real loc[3], P[3], v[3], acc[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+            loc[i] = kind == 0 ? Real(0) : (kind == 1 ? Real(a.os_com[k][i]) : Real(a.pt_local[k][i]));
+        if (b < 0) {   /* a ground point is fixed */
+#pragma unroll
+            for (int i = 0; i < 3; ++i) { P[i] = loc[i]; v[i] = 0; acc[i] = 0; }
+        } else {
+            const int cb = SM.os_cb[b];
+            const Real *kb = lds + LY::KB + 18 * cb;
+            bk_station(kb, lds + LY::AL + 6 * cb, M.os_R[b], SM.os_p[b], loc, P, v, acc);
+            P[0] += x0;
+            if (local && kind != 2) {   /* ground -> the OpenSim body's frame: (R_cb R_os)^T */
+                Real t[3];
+                bk_tmv3(kb, v, t); bk_tmv3(M.os_R[b], t, v);
+                bk_tmv3(kb, acc, t); bk_tmv3(M.os_R[b], t, acc);
+            }
+        }
+        const size_t cnt = kind == 2 ? (size_t)a.npt : (size_t)NOS;
+        const size_t row = ((size_t)idx * cnt + k) * 9, rows = (size_t)a.n * cnt * 9;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            GAT(out, row + i, rows) = P[i]; GAT(out, row + 3 + i, rows) = v[i]; GAT(out, row + 6 + i, rows) = acc[i];
+        }
+    }
+    if (a.orient || a.rot) {
+        for (int b = lane; b < NOS; b += G) {
+            const int cb = SM.os_cb[b];
+            const Real *kb = lds + LY::KB + 18 * cb, *ab = lds + LY::AL + 6 * cb;
+            Real Rb[9], ang[3], w[3], al[3];
+            mm3(kb, M.os_R[b], Rb);
+            body_fixed_xyz(Rb, ang);
+            if (local) { bk_tmv3(Rb, kb + 12, w); bk_tmv3(Rb, ab, al); }
+            else {
+#pragma unroll
+                for (int i = 0; i < 3; ++i) { w[i] = kb[12 + i]; al[i] = ab[i]; }
+            }
+            const size_t r9 = ((size_t)idx * NOS + b) * 9, rows = (size_t)a.n * NOS * 9;
+            if (a.orient) {
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    GAT(a.orient, r9 + i, rows) = ang[i]; GAT(a.orient, r9 + 3 + i, rows) = w[i];
+                    GAT(a.orient, r9 + 6 + i, rows) = al[i];
+                }
+            }
+            if (a.rot) {
+#pragma unroll
+                for (int i = 0; i < 9; ++i) GAT(a.rot, r9 + i, rows) = Rb[i];
+            }
+        }
+    }
+    if (a.system || a.momentum || a.energy) {
+        if (lane < NB) {   /* IC_c: mass centre p3 v3 a3, kinetic energy; WB_c: I_c w_c in ground */
+            const SBody<Real> &bd = SM.body[lane];
+            const Real *kb = lds + LY::KB + 18 * lane;
+            const Real zero[3] = {0, 0, 0}, eye[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+            Real cG[3], vc[3], ac[3], wl[3], Il[3], Iw[3];
+            bk_station(kb, lds + LY::AL + 6 * lane, eye, bd.com, zero, cG, vc, ac);
+            bk_tmv3(kb, kb + 12, wl);
+            Il[0] = bd.inertia[0] * wl[0] + bd.inertia[3] * wl[1] + bd.inertia[4] * wl[2];
+            Il[1] = bd.inertia[3] * wl[0] + bd.inertia[1] * wl[1] + bd.inertia[5] * wl[2];
+            Il[2] = bd.inertia[4] * wl[0] + bd.inertia[5] * wl[1] + bd.inertia[2] * wl[2];
+            mv3(kb, Il, Iw);
+            Real *ic = lds + LY::IC + 10 * lane, *wb = lds + LY::WB + 6 * lane;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) { ic[i] = cG[i]; ic[3 + i] = vc[i]; ic[6 + i] = ac[i]; wb[i] = Iw[i]; }
+            ic[9] = Real(0.5) * (bd.mass * dot3(vc, vc) + dot3(wl, Il));
+        }
+        wave_sync();
+        if (lane == 0) {
+            Real mt = 0, ke = 0, cs[3] = {0, 0, 0}, vs[3] = {0, 0, 0}, as[3] = {0, 0, 0}, hs[3] = {0, 0, 0};
+#pragma unroll 1
+            for (int c = 0; c < NB; ++c) {
+                const Real *ic = lds + LY::IC + 10 * c;
+                const Real m = SM.body[c].mass;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) { cs[i] += m * ic[i]; vs[i] += m * ic[3 + i]; as[i] += m * ic[6 + i]; }
+                mt += m;
+                ke += ic[9];
+            }
+            Real C0[3], V0[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) { C0[i] = cs[i] / mt; V0[i] = vs[i] / mt; }
+#pragma unroll 1
+            for (int c = 0; c < NB; ++c) {   /* angular momentum about the whole-body mass centre */
+                const Real *ic = lds + LY::IC + 10 * c, *wb = lds + LY::WB + 6 * c;
+                const Real m = SM.body[c].mass;
+                Real r[3], dv[3], t[3];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) { r[i] = ic[i] - C0[i]; dv[i] = ic[3 + i] - V0[i]; }
+                cross3(r, dv, t);
+#pragma unroll
+                for (int i = 0; i < 3; ++i) hs[i] += wb[i] + m * t[i];
+            }
+            C0[0] += x0;
+            if (a.system) {
+                const size_t r9 = (size_t)idx * 9, rows = (size_t)a.n * 9;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    GAT(a.system, r9 + i, rows) = C0[i]; GAT(a.system, r9 + 3 + i, rows) = V0[i];
+                    GAT(a.system, r9 + 6 + i, rows) = as[i] / mt;
+                }
+            }
+            if (a.momentum) {
+                const size_t r6 = (size_t)idx * 6, rows = (size_t)a.n * 6;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) { GAT(a.momentum, r6 + i, rows) = vs[i]; GAT(a.momentum, r6 + 3 + i, rows) = hs[i]; }
+            }
+            if (a.energy) {
+                GAT(a.energy, (size_t)idx * 2, (size_t)a.n * 2) = ke;
+                GAT(a.energy, (size_t)idx * 2 + 1, (size_t)a.n * 2) = -mt * dot3(M.gravity, C0);
+            }
+        }
+    }
+}
+
 /* One 256-thread workgroup = 256/G envs of segment `a`, block `blk`.
  * RK: the reference integrator (adaptive Kutta-Merson) instead of the
  * fixed semi-implicit substeps. */
@@ -6119,6 +6339,8 @@ struct Ops {
     int (*jr_launch)(bioim_handle_t *, const JrFields<void> &);
     /* bioim_induced_accel's launcher (every topology); null for an fp32 handle (fp64 kernels only) */
     void (*ia_launch)(bioim_handle_t *, const IaFields<void> &);
+    /* bioim_body_kin's launcher (every topology, both precisions) */
+    void (*bk_launch)(bioim_handle_t *, const BkFields<void> &);
     /* the fused rollout kernel's launcher; null where that instantiation is
      * left out (bioim_rollout then loops over `launch`) */
     void (*rollout)(bioim_handle_t *, const RolloutCall &);
@@ -6411,6 +6633,10 @@ template <class T> void ia_launch_impl(bioim_handle_t *h, const IaFields<void> &
     analysis_launch<IA::EPB>(h, &ia_kernel<T, double>, c, IA::lds_bytes, h->model, h->smodel);
 }
 
+template <class T, typename Real> void bk_launch_impl(bioim_handle_t *h, const BkFields<void> &c) {
+    analysis_launch<BIOIM_EPB>(h, &bk_kernel<T, Real>, c, lds_bytes<T, Real, false>(), h->model, h->smodel);
+}
+
 /* fp32 handles: the fp64 DModel / SModel of jr_kernel, built from the pack
  * and uploaded on the handle's first bioim_joint_reaction (that call blocks
  * for the two copies; handles that never ask for joint reactions carry
@@ -6467,6 +6693,7 @@ template <class T, typename Real> int upload_smodel(bioim_handle_t *h) {
     if constexpr (std::is_same<Real, double>::value) ALLOW_LDS((ik_kernel<T, double>), (lds_bytes<T, double, false>()));
     ALLOW_LDS((jr_kernel<T, Real>), (lds_bytes<T, double, false>()));
     if constexpr (std::is_same<Real, double>::value) ALLOW_LDS((ia_kernel<T, double>), (IaLay<T, double>::lds_bytes));
+    ALLOW_LDS((bk_kernel<T, Real>), (lds_bytes<T, Real, false>()));
     constexpr size_t B = smodel_bytes<T, Real>();
     std::vector<unsigned char> img(B, 0);
     build_smodel<T, Real>(h->pack, *reinterpret_cast<SModel<T, Real> *>(img.data()));
@@ -6488,6 +6715,8 @@ template <class T> bool pick(const bioim_modelpack_t &p, int precision, Ops &ops
     ops.ia_launch = precision == 64 ? &ia_launch_impl<T> : nullptr;
     if (precision == 64) ops.jr_launch = &jr_launch_impl<T, double>;
     else ops.jr_launch = &jr_launch_impl<T, float>;
+    if (precision == 64) ops.bk_launch = &bk_launch_impl<T, double>;
+    else ops.bk_launch = &bk_launch_impl<T, float>;
     if constexpr (T::NM > 0) {
         if (precision == 64) ops.ma_launch = &ma_launch_impl<T, double>;
         else ops.ma_launch = &ma_launch_impl<T, float>;
@@ -7290,6 +7519,39 @@ int bioim_induced_accel(bioim_handle_t *h, int n, const void *q, const void *u, 
     const IaFields<void> c{n, kind, force_threshold, q, u, ft, tau_act, ext, cpoint, cactive,
                            accel, com_accel, reaction, cpoint_out, cactive_out, status};
     h->ops.ia_launch(h, c);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int bioim_body_kin(bioim_handle_t *h, int n, const void *q, const void *u, const void *qdd, int npt,
+                   const int32_t *pt_body, const void *pt_local, int flags, void *origin, void *com, void *orient,
+                   void *rot, void *system, void *momentum, void *energy, void *point) {
+    if (!h) return fail(BIOIM_E_ARG, "bioim_body_kin: null handle");
+    if (n < 0) return fail(BIOIM_E_ARG, "bioim_body_kin: negative n");
+    if (npt < 0 || npt > BIOIM_BK_MAX_POINTS)
+        return fail(BIOIM_E_ARG, "bioim_body_kin: npt must be in [0, BIOIM_BK_MAX_POINTS]");
+    if (npt > 0 && (!pt_body || !pt_local)) return fail(BIOIM_E_ARG, "bioim_body_kin: null point table");
+    for (int i = 0; i < npt; ++i)
+        if (pt_body[i] < -1 || pt_body[i] >= h->pack.nosbody)
+            return fail(BIOIM_E_ARG, "bioim_body_kin: a point's body index is outside [-1, nosbody)");
+    if (flags & ~BIOIM_BK_LOCAL) return fail(BIOIM_E_ARG, "bioim_body_kin: unknown flag bits");
+    if (n > 0 && !q) return fail(BIOIM_E_ARG, "bioim_body_kin: null q");
+    if (!origin && !com && !orient && !rot && !system && !momentum && !energy && !point)
+        return fail(BIOIM_E_ARG, "bioim_body_kin: no output requested");
+    if (n == 0) return 0;
+    HIPCHK(hipSetDevice(h->device));
+    BkFields<void> c{};
+    c.n = n; c.npt = npt; c.flags = flags;
+    c.q = q; c.u = u; c.qdd = qdd;
+    c.origin = origin; c.com = com; c.orient = orient; c.rot = rot;
+    c.system = system; c.momentum = momentum; c.energy = energy; c.point = point;
+    for (int b = 0; b < h->pack.nosbody; ++b)
+        for (int i = 0; i < 3; ++i) c.os_com[b][i] = h->pack.osbody[b].com[i];
+    for (int i = 0; i < npt; ++i) {
+        c.pt_body[i] = (int8_t)pt_body[i];
+        for (int k = 0; k < 3; ++k) c.pt_local[i][k] = static_cast<const double *>(pt_local)[3 * i + k];
+    }
+    h->ops.bk_launch(h, c);
     HIPCHK(hipGetLastError());
     return 0;
 }

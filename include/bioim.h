@@ -482,6 +482,67 @@ int bioim_induced_accel(bioim_handle_t *h, int n, const void *q, const void *u /
         double force_threshold,
         void *accel /* [n][NC][ndof] */, void *com_accel /* [n][NC][3] */, void *reaction /* [n][NC][ncforce][3] */,
         void *cpoint_out /* [n][ncforce][3] */, uint8_t *cactive_out /* [n][ncforce] */, int32_t *status /* [n] */);
+/* Body kinematics (OpenSim's BodyKinematics and PointKinematics analyses, the
+ * kinematics-analysis stage between IK and MuscleAnalysis) at n arbitrary
+ * states, not the handle's envs: the env state and the realize cache are
+ * neither read nor written.  Both precisions, every topology (no muscle is
+ * involved).  q, u, qdd [n][ndof] are device pointers in the handle's
+ * precision, dof order as for bioim_id_eval; u, qdd NULL: zeros, bit for bit.
+ * A body's spatial acceleration is a_k = AL_k + sum over the dofs d on k's
+ * root path of S_d q''_d (bioim_joint_reaction's definition).
+ *
+ * Points.  npt points, 0 .. BIOIM_BK_MAX_POINTS, shared by all states:
+ *   pt_body  [npt] int32   HOST array: OpenSim body index (the pack's osbody
+ *                          order), -1 = ground;
+ *   pt_local [npt][3]      HOST array of doubles (either precision): the
+ *                          point in that OpenSim body's frame.
+ * Both are read and checked before the call returns and travel to the kernel
+ * inside its argument list, so the caller may reuse them at once and a bad
+ * body index is refused before any launch.  BIOIM_BK_MAX_POINTS is 64: with the
+ * OpenSim bodies' mass centres the tables take 2.2 KiB of the 4 KiB a kernel's
+ * arguments may have; the kernel itself keeps no per-point storage.
+ *
+ * Outputs (device pointers in the handle's precision; any may be NULL, not
+ * all).  Bodies in the pack's OpenSim-body order; [3][3] rows are position,
+ * velocity, acceleration (x y z each), in the ground frame:
+ *   origin   [n][nosbody][3][3]  each OpenSim body frame's origin;
+ *   com      [n][nosbody][3][3]  each OpenSim body's own mass centre
+ *                                (osbody.com; what BodyKinematics reports);
+ *   orient   [n][nosbody][3][3]  body-fixed XYZ angles of R = Rx Ry Rz, angular
+ *                                velocity, angular acceleration;
+ *   rot      [n][nosbody][9]     R (body -> ground), row-major;
+ *   system   [n][3][3]           the whole-body mass centre;
+ *   momentum [n][2][3]           linear momentum sum m_k v_k, and angular
+ *                                momentum about the whole-body mass centre,
+ *                                sum R_k I_k R_k^T w_k + m_k (c_k - C) x (v_k - V);
+ *   energy   [n][2]              kinetic energy sum (m_k v_k^2 + w_k . I_k w_k)/2
+ *                                and gravitational potential energy -m g . C;
+ *   point    [n][npt][3][3]      each listed point; a ground point is fixed
+ *                                (its position is pt_local, the rest zeros).
+ * The sums run over the composite bodies k in index order (c_k, v_k their mass
+ * centres, m the sum of their masses).
+ * flags: BIOIM_BK_LOCAL is OpenSim's express_results_in_body_local_frame: the
+ * linear velocity and acceleration in origin and com and the angular velocity
+ * and acceleration in orient are expressed in the OpenSim body's own frame;
+ * positions, angles and every other output stay in the ground frame.
+ * No status output: a NaN in q, u or qdd simply comes out.  A state's result
+ * does not depend on n or on the other states, and a repeated call repeats it
+ * bit for bit; origins, mass centres and points go through one piece of code,
+ * so a point at a body's origin (or at osbody.com) equals that body's origin
+ * (com) row bit for bit.  BIOIM_E_ARG, before any device call and in this
+ * order, for: a null handle, n < 0, npt < 0 or npt > BIOIM_BK_MAX_POINTS, a
+ * null point table with npt > 0, a body index outside [-1, nosbody), unknown
+ * flag bits, null q with n > 0, every output NULL.  n == 0 returns BIOIM_OK
+ * without a launch.  Asynchronous on the handle's stream; synchronizes
+ * nothing. */
+#define BIOIM_BK_MAX_POINTS 64
+#define BIOIM_BK_LOCAL 1   /* flags: velocities and accelerations in the body's own frame */
+int bioim_body_kin(bioim_handle_t *h, int n, const void *q, const void *u /* NULL: 0 */, const void *qdd /* NULL: 0 */,
+        int npt, const int32_t *pt_body /* host [npt]: OpenSim body index, -1 = ground */,
+        const void *pt_local /* host double [npt][3], in that body's frame */, int flags /* BIOIM_BK_LOCAL */,
+        void *origin /* [n][nosbody][3][3] */, void *com /* [n][nosbody][3][3] */, void *orient /* [n][nosbody][3][3] */,
+        void *rot /* [n][nosbody][9] */, void *system /* [n][3][3] */, void *momentum /* [n][2][3] */,
+        void *energy /* [n][2] */, void *point /* [n][npt][3][3] */);
 /* OsimModel calls on single envs (the reference's physics facade,
  * opensim_wrapper.py:92-332), for callers that drive the model directly
  * (tests/example_position_control.py:203-223; the env methods
