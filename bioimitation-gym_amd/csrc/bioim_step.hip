@@ -294,7 +294,7 @@ template <int G> DEV bool group_any(bool p) {
 }
 
 #ifdef BIOIM_STAMPS
-__device__ unsigned long long g_stamps[24];
+__device__ unsigned long long g_stamps[28];
 #endif
 /* Diagnostic build only (-DBIOIM_WAVETIME, single translation unit,
  * tools/wavetime.py): shader cycles of every wave of the last step launch */
@@ -1081,16 +1081,42 @@ template <class T, typename Real> DEV void compose(Frame<Real> &F, const Real *l
 }
 
 /* identity joint (LOC slot NB) and the ground frame (KB/AL slot NB) */
-template <class T, typename Real> DEV void kin_ground(Real *lds, Real x0) {
+/* BIOIM_GROUND_ONCE (the step kernels): the ground slot's constants — the KB
+ * rotation, its zero origin / velocity words and the zero AL row, which no
+ * other code writes — go to LDS once per launch (kin_ground_const) and a call
+ * writes only kb[9] = -x0.  The identity LOC slot lies in the union region:
+ * where the call's force slots (TAU, CJ) end below it (ground_loc_free), only
+ * the report's staging (OBS, REP) writes over it, and it is written once per
+ * launch too and again before a realize that follows a report (the reset
+ * realize); elsewhere (the spatial muscle topologies) it stays with the call.
+ * Bits (TailSwitch): 1 the planar topologies' kernels, 2 the spatial ones',
+ * 4 the fused two-topology kernels (env_kernel2, rollout_kernel2), which
+ * measured no faster with it (C5 0.4687 -> 0.4708 ms same box) and keep the
+ * per-call writes. */
+#ifndef BIOIM_GROUND_ONCE
+#define BIOIM_GROUND_ONCE 3
+#endif
+template <class T, typename Real> DEV constexpr bool ground_loc_free() {
     using LY = Lay<T, Real>;
-    Real *lc = lds + LY::LOC + 24 * T::NB, *kb = lds + LY::KB + 18 * T::NB, *ab = lds + LY::AL + 6 * T::NB;
+    return LY::LOC + 24 * T::NB >= LY::TAU + LY::TAUN && LY::LOC + 24 * T::NB >= LY::CJ + LY::NS * LY::CJN;
+}
+template <class T, typename Real> DEV void kin_ground_loc(Real *lds) {
+    Real *lc = lds + Lay<T, Real>::LOC + 24 * T::NB;
 #pragma unroll
     for (int i = 0; i < 24; ++i) lc[i] = (i < 9 && (i % 4) == 0) ? Real(1) : Real(0);
+}
+template <class T, typename Real> DEV void kin_ground_const(Real *lds) {
+    using LY = Lay<T, Real>;
+    Real *kb = lds + LY::KB + 18 * T::NB, *ab = lds + LY::AL + 6 * T::NB;
 #pragma unroll
     for (int i = 0; i < 18; ++i) kb[i] = (i < 9 && (i % 4) == 0) ? Real(1) : Real(0);
-    kb[9] = -x0;
 #pragma unroll
     for (int i = 0; i < 6; ++i) ab[i] = 0;
+}
+template <class T, typename Real, bool ONCE = false> DEV void kin_ground(Real *lds, Real x0) {
+    if constexpr (!ONCE || !ground_loc_free<T, Real>()) kin_ground_loc<T, Real>(lds);
+    if constexpr (!ONCE) kin_ground_const<T, Real>(lds);
+    lds[Lay<T, Real>::KB + 18 * T::NB + 9] = -x0;
 }
 
 /* Phase 1b (lane = body c): compose c's root-to-body joint chain in
@@ -1863,7 +1889,12 @@ template <class T, bool IMP = true> struct BfSwitch {
     static constexpr bool ME = BFK || (BF3 && (BIOIM_BF3 & 128));
 };
 
-template <class T, typename Real, bool PERT, bool BF_ROWS, bool IMP, bool CACHE = false>
+/* The step-tail switch of one kernel family (BIOIM_GROUND_ONCE's bits) */
+template <class T, bool FUSED = false> struct TailSwitch {
+    static constexpr int BIT = FUSED ? 4 : (T::PLANAR ? 1 : 2);
+    static constexpr bool GROUND = (BIOIM_GROUND_ONCE & BIT) != 0;
+};
+template <class T, typename Real, bool PERT, bool BF_ROWS, bool IMP, bool CACHE = false, class TS = TailSwitch<T>>
 DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Real ud,
                   const Real (&act)[Lay<T, Real>::MPL], const Real (&lce)[Lay<T, Real>::MPL],
                   const Real (&control)[Lay<T, Real>::MPL], int lane, Real *lds, Real h, bool equilibrate,
@@ -1954,7 +1985,7 @@ DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Rea
 
     /* ---- phase 1: lane-parallel kinematics */
     if (lane < NB) kin_local<T, Real>(SM, lds, lane);
-    if (lane == NB) kin_ground<T, Real>(lds, x0);
+    if (lane == NB) kin_ground<T, Real, TS::GROUND>(lds, x0);
     wave_sync();
     STAMP(0);
     if (lane < NB) kin_chain<T, Real>(SM, lds, lane, x0);
@@ -4735,9 +4766,10 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_e
 /* One 256-thread workgroup = 256/G envs of segment `a`, block `blk`.
  * RK: the reference integrator (adaptive Kutta-Merson) instead of the
  * fixed semi-implicit substeps. */
-template <class T, typename Real, bool PERT, bool RK, bool REP>
+template <class T, typename Real, bool PERT, bool RK, bool REP, bool FUSED = false>
 DEV void env_block(const LaunchArgs<T, Real> &a, int blk) {
     using LY = Lay<T, Real>;
+    using TS = TailSwitch<T, FUSED>;
     constexpr int G = T::G, ND = LY::ND, NA = T::NA, NM = T::NM;
     constexpr int EPB = BIOIM_EPB;
     constexpr size_t SMB = smodel_bytes<T, Real>();
@@ -4783,6 +4815,14 @@ DEV void env_block(const LaunchArgs<T, Real> &a, int blk) {
         if (a.active && !GAT(a.active, env, N) && !(RK && GAT(st.pend, env, (size_t)N) != 0)) return;
     }
     const int H = M.horizon;
+    /* the ground slot's constants, once per launch (kin_ground); the first
+     * call's own syncs come before their first read */
+    if constexpr (TS::GROUND) {
+        if (lane == T::NB) {
+            kin_ground_const<T, Real>(lds);
+            if constexpr (ground_loc_free<T, Real>()) kin_ground_loc<T, Real>(lds);
+        }
+    }
     constexpr int MPL = LY::MPL;                  /* muscles / actions per lane: m = lane + j*G */
     constexpr int CPL = (T::NC + G - 1) / G;      /* coordinates per lane (report)              */
     Dyn<T, Real> D;
@@ -5028,6 +5068,16 @@ DEV void env_block(const LaunchArgs<T, Real> &a, int blk) {
      * at the end state; a reset (mode 1, or auto-reset after done) loads the
      * reference row and folds the muscle fiber equilibrium into its realize. */
     bool pending_reset = (mode == 1), reported_reset = false;
+#ifdef BIOIM_STAMPS
+    /* the prologue, kernel start to loop entry with its loads landed (the
+     * staging, slot 11, is part of it) */
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_waitcnt(0x0070);
+    const unsigned long long k_t2 = __builtin_amdgcn_s_memtime();
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    if (blockIdx.x == 0 && threadIdx.x == 0) g_stamps[22] += k_t2 - k_t0;
+    __builtin_amdgcn_sched_barrier(0);
+#endif
     for (;;) {
         if constexpr (RK) {
             if (remaining > 0 && rk_stage == 0) {   /* start an RK step, or stop */
@@ -5074,6 +5124,11 @@ DEV void env_block(const LaunchArgs<T, Real> &a, int blk) {
                 if constexpr (CACHE) D.ms[j].vN = 0;
             }
             resets += 1;
+            /* an auto-reset's realize follows a report, whose staging (OBS,
+             * REP) lies over the identity LOC slot: written again (the
+             * report's last LDS reads are behind its closing sync) */
+            if constexpr (TS::GROUND && ground_loc_free<T, Real>())
+                if (lane == T::NB) kin_ground_loc<T, Real>(lds);
         }
         if constexpr (CACHE) {
             /* the first substep from the cache; a realize (step or reset) forms
@@ -5114,7 +5169,7 @@ DEV void env_block(const LaunchArgs<T, Real> &a, int blk) {
             /* RK: explicit accelerations (h = 0, the implicit terms compile away) */
             /* branch-free phase-3 row stores, except in the spatial RK kernels
              * (they would take those kernels past the 512-register budget) */
-            dynamics<T, Real, PERT, !RK || T::PLANAR, !RK, CACHE>(*(const DModel<Real> *)Mi, SM, qd, ud, act, lce, control, lane, lds,
+            dynamics<T, Real, PERT, !RK || T::PLANAR, !RK, CACHE, TS>(*(const DModel<Real> *)Mi, SM, qd, ud, act, lce, control, lane, lds,
                                     RK ? Real(0) : (sub ? dt : Real(0)), eq && NM > 0, PA, pslot,
                                     RK ? 0 : M.nsub - remaining, D, CI);
         }
@@ -5181,6 +5236,12 @@ DEV void env_block(const LaunchArgs<T, Real> &a, int blk) {
             continue;
         }
         if (!RK && sub) {
+#ifdef BIOIM_STAMPS
+            __builtin_amdgcn_sched_barrier(0);
+            const unsigned long long su_t0 = __builtin_amdgcn_s_memtime();
+            __builtin_amdgcn_s_waitcnt(0xC07F);
+            __builtin_amdgcn_sched_barrier(0);
+#endif
             if (lane < ND) { ud += dt * D.qdd; qd += dt * ud; }
             if constexpr (NM > 0) {
 #pragma unroll
@@ -5202,6 +5263,18 @@ DEV void env_block(const LaunchArgs<T, Real> &a, int blk) {
                     }
                 }
             }
+#ifdef BIOIM_STAMPS
+            {   /* the substep update of the first env of workgroup 0: its results pinned, then the clock */
+                asm volatile("" : "+v"(qd), "+v"(ud));
+#pragma unroll
+                for (int j = 0; j < MPL; ++j) asm volatile("" : "+v"(act[j]), "+v"(lce[j]));
+                __builtin_amdgcn_sched_barrier(0);
+                const unsigned long long su_t1 = __builtin_amdgcn_s_memtime();
+                __builtin_amdgcn_s_waitcnt(0xC07F);
+                if (blockIdx.x == 0 && threadIdx.x == 0) g_stamps[24] += su_t1 - su_t0;
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#endif
             --remaining;
             continue;
         }
@@ -5556,7 +5629,12 @@ DEV void env_block(const LaunchArgs<T, Real> &a, int blk) {
     }
 
 #ifdef BIOIM_STAMPS
-    if (blockIdx.x == 0 && threadIdx.x == 0) g_stamps[10] += __builtin_amdgcn_s_memtime() - k_t1;
+    __builtin_amdgcn_sched_barrier(0);
+    const unsigned long long k_t3 = __builtin_amdgcn_s_memtime();
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    /* slot 10: staging barrier to loop exit (as before); slot 25: the loop alone */
+    if (blockIdx.x == 0 && threadIdx.x == 0) { g_stamps[10] += k_t3 - k_t1; g_stamps[25] += k_t3 - k_t2; }
+    __builtin_amdgcn_sched_barrier(0);
 #endif
     /* ---- store state */
         if (lane == 0) {
@@ -5612,6 +5690,11 @@ DEV void env_block(const LaunchArgs<T, Real> &a, int blk) {
         if (NM > 0 && m < NM) { GAT(st.act, (size_t)m * N + env, (size_t)(NM > 0 ? NM : 1) * N) = act[j]; GAT(st.lce, (size_t)m * N + env, (size_t)(NM > 0 ? NM : 1) * N) = lce[j]; }
         if (!REP && m < NA) GAT(st.last, (size_t)m * N + env, (size_t)NA * N) = last[j];
     }
+#ifdef BIOIM_STAMPS
+    /* the epilogue: loop exit to the state write-back issued */
+    __builtin_amdgcn_sched_barrier(0);
+    if (blockIdx.x == 0 && threadIdx.x == 0) g_stamps[23] += __builtin_amdgcn_s_memtime() - k_t3;
+#endif
 }
 
 /* REP: the OsimModel-call kernels (mode 2, bioim_osim): the same code plus
@@ -5642,8 +5725,8 @@ template <class T0, class T1, typename Real>
 __global__ __launch_bounds__(BIOIM_EPB * T0::G) __attribute__((amdgpu_waves_per_eu(1, 1))) void env_kernel2(
     LaunchArgs<T0, Real> a0, LaunchArgs<T1, Real> a1) {
     static_assert(T0::G == T1::G, "a fused launch needs one workgroup shape");
-    if ((int)blockIdx.x < a0.blocks) env_block<T0, Real, false, false, false>(a0, blockIdx.x);
-    else env_block<T1, Real, false, false, false>(a1, blockIdx.x - a0.blocks);
+    if ((int)blockIdx.x < a0.blocks) env_block<T0, Real, false, false, false, true>(a0, blockIdx.x);
+    else env_block<T1, Real, false, false, false, true>(a1, blockIdx.x - a0.blocks);
 }
 
 /* Fused multi-step rollout (bioim_rollout): `steps` consecutive env steps of
@@ -5854,7 +5937,7 @@ step:
         asm volatile("" : "+s"(a.act_stride), "+s"(a.obs_stride), "+s"(a.info_stride));
         asm volatile("" : "+s"(a.st.q), "+s"(a.st.u), "+s"(a.st.act), "+s"(a.st.lce), "+s"(a.st.hist), "+s"(a.st.last));
         asm volatile("" : "+s"(a.st.vnw), "+s"(a.st.cache), "+s"(a.st.cache_ok));
-        env_block<T, Real, false, false, false>(a, blk);
+        env_block<T, Real, false, false, false, true>(a, blk);
     }
 meet:
     {
@@ -7900,9 +7983,9 @@ int bioim_debug_fviter(unsigned *out, int n) {
 #ifdef BIOIM_STAMPS
 int bioim_debug_stamps(unsigned long long *out, int reset) {
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps), sizeof(unsigned long long) * 24));
+    HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps), sizeof(unsigned long long) * 28));
     if (reset) {
-        unsigned long long z[24] = {0};
+        unsigned long long z[28] = {0};
         HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), z, sizeof(z)));
     }
     return 0;

@@ -1,8 +1,10 @@
-"""Per-phase cycle shares of the dynamics substep (diagnostic build
-libbioim_stamps.so, -DBIOIM_STAMPS).  Read the shares, not absolute times."""
+"""Per-phase cycle shares of the dynamics substep and of the launch around it
+(diagnostic build libbioim_stamps.so, -DBIOIM_STAMPS, tools/build_stamps.sh;
+BIOIM_LIB names another stamped build).  Read the shares, not absolute times.
+  python tools/stamps.py [precision] [env id] [--rk]"""
 import ctypes as C, os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-os.environ['BIOIM_LIB'] = os.path.join(REPO, 'bioimitation-gym_amd', 'build', 'libbioim_stamps.so')
+os.environ.setdefault('BIOIM_LIB', os.path.join(REPO, 'bioimitation-gym_amd', 'build', 'libbioim_stamps.so'))
 sys.path[:0] = [os.path.join(REPO, 'bioimitation-gym_amd')]
 import numpy as np, torch
 from bioimitation import _lib
@@ -19,7 +21,7 @@ env = VectorEnv(env_id, 4096, config={'integrator': 'rk-merson'} if rk else None
 if rk:
     env.set_rk_budget(6)
 env.reset()
-buf = (C.c_ulonglong * 24)()
+buf = (C.c_ulonglong * 28)()
 steps = 30
 acts = torch.rand((steps + 5, 4096, env.action_dim), device=env.device, dtype=env.dtype)
 for k in range(5):
@@ -40,6 +42,18 @@ for i, n in enumerate(names):
     print(f'  {n:32s} {buf[i] / calls:9.0f} cyc  {100.0 * buf[i] / tot:5.1f} %')
 print(f'  per launch: loop {buf[10] / steps:.0f} cyc, of which dynamics {tot / steps:.0f}; '
       f'model-image staging {buf[11] / steps:.0f} cyc')
+rep_cyc = buf[19] + buf[20]
+if buf[25]:
+    # around the calls: prologue (kernel start to loop entry, loads landed; staging included), the loop's
+    # time outside dynamics split into the substep updates, the reports and the rest, and the epilogue
+    loop = buf[25]
+    rest = loop - tot - buf[24] - rep_cyc
+    iters = calls
+    print(f'  per launch: prologue {buf[22] / steps:.0f} cyc (staging {buf[11] / steps:.0f}), loop {loop / steps:.0f}, '
+          f'epilogue {buf[23] / steps:.0f}')
+    print(f'  loop outside dynamics {(loop - tot) / steps:.0f} cyc per launch ({100.0 * (loop - tot) / loop:.1f} % of the loop): '
+          f'substep updates {buf[24] / steps:.0f} ({buf[24] / max(1, steps * env.nsub):.0f} per substep), '
+          f'reports {rep_cyc / steps:.0f}, rest {rest / steps:.0f} ({rest / iters:.0f} per iteration)')
 if buf[21]:
     print(f'  report (wg 0, env 0): {buf[21]} reports, per report: observation {buf[19] / buf[21]:.0f} cyc, '
           f'reward + done + writes {buf[20] / buf[21]:.0f} cyc')
