@@ -853,7 +853,85 @@ DEV void publish_coords(const DModel<Real> &M, const SModel<T, Real> &SM, Real *
  * giving the child-in-parent transform, the joint's relative velocity and
  * velocity-product acceleration in the parent frame, and the joint's
  * Plucker columns about the parent origin (accumulated per dof into SL). */
-template <class T, typename Real>
+/* BIOIM_FRONTEND (the step kernels' dynamics calls; the analysis kernels
+ * reach these helpers through state_kinematics with FE = 0, the forms below
+ * without it): waits and duplicate LDS traffic taken out of the kinematics
+ * front end, every arithmetic operation and its order kept.  One bit per item:
+ *   1 (FE_COLS)    kin_local sums a body's joint columns per local dof in
+ *                  registers (0 + its axes' contributions, in axis order) and
+ *                  stores each dof's words to SL once: no read-modify-write of
+ *                  SL at a run-time dof index, no per-call zeroing of SL, and
+ *                  an axis without a dof contributes to nothing (no sink row)
+ *   2 (FE_KINDS)   planar kin_local: the linear / constant axis forms are
+ *                  computed from unconditional loads and selected (as the
+ *                  spline arm), no EXEC-masked arm per kind
+ *   4 (FE_INERTIA) kin_chain hands its frame to body_inertia in registers, in
+ *                  the same body-lane block: no reload of KB / AL, and the
+ *                  columns run with the subtree sums' reads (one sync fewer)
+ *   8 (FE_LEVEL0)  the chain's first level composes with the ground frame
+ *                  (R = I, o = (-x0, 0, 0), no motion) by copy and offset
+ * One byte per kernel family (TailSwitch): bits 0-7 the planar topologies'
+ * kernels, 8-15 the spatial ones', 16-23 the fused two-topology kernels.
+ * Shipped (same-box A/B): all four in the planar kernels.  None in
+ * the spatial ones: FE_LEVEL0 changes result bits there (the fused kernels and
+ * the parent build no longer agree with them bit for bit), FE_INERTIA alone
+ * puts one spatial RK kernel on scratch, and FE_COLS | FE_INERTIA gained less
+ * than the builds' round spread on Running3D.  None in the fused kernels, which
+ * measured no faster with any of them. */
+#ifndef BIOIM_FRONTEND
+#define BIOIM_FRONTEND 0x00000F
+#endif
+constexpr int FE_COLS = 1, FE_KINDS = 2, FE_INERTIA = 4, FE_LEVEL0 = 8;
+
+/* a body's dofs as kin_local meets them: the local slot of (body, axis) is
+ * the rank of the axis's dof among the body's distinct dofs in axis order */
+template <class T> struct BodyDofs {
+    static constexpr int dof_of(int b, int ax) {
+        const int co = T::axis_coord[b * 6 + ax];
+        return co >= 0 ? T::coord_dof[co] : -1;
+    }
+    static constexpr int slot(int b, int ax) {
+        const int d = dof_of(b, ax);
+        if (d < 0) return -1;
+        int n = 0;
+        for (int a = 0; a < ax; ++a) {
+            const int e = dof_of(b, a);
+            if (e < 0) continue;
+            bool seen = false;
+            for (int a2 = 0; a2 < a; ++a2) seen = seen || dof_of(b, a2) == e;
+            if (e == d) return n;
+            n += seen ? 0 : 1;
+        }
+        return n;
+    }
+    static constexpr int count(int b) {
+        int n = 0;
+        for (int ax = 0; ax < 6; ++ax) n = slot(b, ax) + 1 > n ? slot(b, ax) + 1 : n;
+        return n;
+    }
+    static constexpr int max_count() {
+        int n = 1;
+        for (int b = 0; b < T::NB; ++b) n = count(b) > n ? count(b) : n;
+        return n;
+    }
+    static constexpr int dof(int b, int k) {
+        for (int ax = 0; ax < 6; ++ax)
+            if (slot(b, ax) == k) return dof_of(b, ax);
+        return -1;
+    }
+    /* every dof is a local dof of exactly one body (its SL row has one writer) */
+    static constexpr bool covers_all() {
+        for (int d = 0; d < T::ND; ++d) {
+            int n = 0;
+            for (int b = 0; b < T::NB; ++b)
+                for (int k = 0; k < count(b); ++k) n += dof(b, k) == d ? 1 : 0;
+            if (n != 1) return false;
+        }
+        return true;
+    }
+};
+
+template <class T, typename Real, int FE = 0>
 DEV void kin_local(const SModel<T, Real> &SM, Real *lds, int c) {
     using LY = Lay<T, Real>;
     using PL = Planar<T>;
@@ -863,7 +941,7 @@ DEV void kin_local(const SModel<T, Real> &SM, Real *lds, int c) {
     Real RFM[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     Real wrel[3] = {0, 0, 0}, arel[3] = {0, 0, 0}, pFM[3] = {0, 0, 0}, pd[3] = {0, 0, 0}, pdd[3] = {0, 0, 0};
     Real col[6][3];
-    int cd[6];
+    int cd[6];   /* the axis's dof; FE_COLS: its local slot (BodyDofs) */
     sfor<0, 6>([&](auto aI) {
         constexpr int ax = decltype(aI)::value;
         cd[ax] = -1;
@@ -888,7 +966,8 @@ DEV void kin_local(const SModel<T, Real> &SM, Real *lds, int c) {
                 constexpr int dc = co >= 0 ? T::coord_dof[co] : -1, jsl = TopoInfo<T>::jslot(bb, ax);
                 kind = cb == bb ? k : kind;
                 cc = cb == bb ? co : cc;
-                dof = cb == bb ? dc : dof;
+                constexpr int dl = (FE & FE_COLS) ? BodyDofs<T>::slot(bb, ax) : dc;
+                dof = cb == bb ? dl : dof;
                 js = cb == bb ? jsl : js;
             });
             const int cs = cc >= 0 ? cc : 0;
@@ -898,11 +977,21 @@ DEV void kin_local(const SModel<T, Real> &SM, Real *lds, int c) {
             constexpr unsigned KM = TopoInfo<T>::axis_kinds(ax);
             const Real fa = b.fa[ax], fb = b.fb[ax];
             Real f = 0, f1 = 0, f2 = 0;
-            if constexpr ((KM & (1u << (BIOIM_FN_LINEAR + 1))) != 0) {
-                if (kind == BIOIM_FN_LINEAR) { f = fa * qc + fb; f1 = fa; }
-            }
-            if constexpr ((KM & (1u << (BIOIM_FN_CONST + 1))) != 0) {
-                if (kind == BIOIM_FN_CONST) f = fb;
+            if constexpr ((FE & FE_KINDS) && T::PLANAR) {
+                /* both forms from the loads above, selected */
+                if constexpr ((KM & (1u << (BIOIM_FN_LINEAR + 1))) != 0) {
+                    const bool li = kind == BIOIM_FN_LINEAR;
+                    const Real lf = fa * qc + fb;
+                    f = li ? lf : f; f1 = li ? fa : f1;
+                }
+                if constexpr ((KM & (1u << (BIOIM_FN_CONST + 1))) != 0) f = kind == BIOIM_FN_CONST ? fb : f;
+            } else {
+                if constexpr ((KM & (1u << (BIOIM_FN_LINEAR + 1))) != 0) {
+                    if (kind == BIOIM_FN_LINEAR) { f = fa * qc + fb; f1 = fa; }
+                }
+                if constexpr ((KM & (1u << (BIOIM_FN_CONST + 1))) != 0) {
+                    if (kind == BIOIM_FN_CONST) f = fb;
+                }
             }
             if constexpr ((KM & (1u << (BIOIM_FN_SPLINE + 1))) != 0) {
                 /* spline axes: evaluated in phase 0b.  Planar: loaded
@@ -996,6 +1085,62 @@ DEV void kin_local(const SModel<T, Real> &SM, Real *lds, int c) {
     mv3m<ZR, 0>(Rpf, pFM, pM);
 #pragma unroll
     for (int i = 0; i < 3; ++i) pM[i] += b.p_pf[i];
+    if constexpr ((FE & FE_COLS) != 0) {
+        /* per local dof slot k: 0 + the contributions of the axes that move
+         * it, in axis order (selects; an axis without a dof matches no slot),
+         * then one plain store of the dof's words */
+        constexpr int NLS = BodyDofs<T>::max_count();
+        static_assert(BodyDofs<T>::covers_all(), "FE_COLS: one body lane stores each dof's SL row");
+        Real acc[NLS][6];
+#pragma unroll
+        for (int k = 0; k < NLS; ++k)
+#pragma unroll
+            for (int i = 0; i < 6; ++i) acc[k][i] = 0;
+        sfor<0, 6>([&](auto aI) {
+            constexpr int ax = decltype(aI)::value;
+            if constexpr (((USED >> ax) & 1u) != 0) {
+                Real v[3], lin[3] = {0, 0, 0};
+                if constexpr (ax < 3) {
+                    mv3m<ZR, ZW>(Rpf, col[ax], v);
+                    cross3m<0, ZW>(pM, v, lin);
+                } else {
+                    mv3m<ZR, ZV>(Rpf, col[ax], v);
+                }
+#pragma unroll
+                for (int k = 0; k < NLS; ++k) {
+                    const bool on = cd[ax] == k;
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) {
+                        if constexpr (ax < 3) {
+                            if (!((ZW >> i) & 1u)) acc[k][i] = on ? acc[k][i] + v[i] : acc[k][i];
+                            if (!((ZV >> i) & 1u)) acc[k][3 + i] = on ? acc[k][3 + i] + lin[i] : acc[k][3 + i];
+                        } else {
+                            if (!((ZV >> i) & 1u)) acc[k][3 + i] = on ? acc[k][3 + i] + v[i] : acc[k][3 + i];
+                        }
+                    }
+                }
+            }
+        });
+        int cb = c;
+        if constexpr (!T::PLANAR) asm volatile("" : "+v"(cb));
+        sfor<0, NLS>([&](auto kI) {
+            constexpr int k = decltype(kI)::value;
+            int dk = -1;
+            sfor<0, T::NB>([&](auto bI) {
+                constexpr int bb = decltype(bI)::value;
+                constexpr int dbk = BodyDofs<T>::dof(bb, k);
+                dk = cb == bb ? dbk : dk;
+            });
+            if (dk >= 0) {
+                Real *sl = lds + LY::SL + 6 * dk;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    if (!((ZW >> i) & 1u)) sl[i] = acc[k][i];
+                    if (!((ZV >> i) & 1u)) sl[3 + i] = acc[k][3 + i];
+                }
+            }
+        });
+    } else
     sfor<0, 6>([&](auto aI) {
         constexpr int ax = decltype(aI)::value;
         if constexpr (((USED >> ax) & 1u) != 0) {
@@ -1080,6 +1225,31 @@ template <class T, typename Real> DEV void compose(Frame<Real> &F, const Real *l
     PL::rot(F.R); PL::ang(F.w); PL::lin(F.vO); PL::ang(F.al); PL::lin(F.aO);
 }
 
+/* FE_LEVEL0: compose() for the chain's first level, whose F is the ground
+ * frame (R = I, o = (-x0, 0, 0), no motion): the same values without the
+ * products with those constants (equal for finite inputs up to the sign of a
+ * zero) */
+template <class T, typename Real> DEV void compose_ground(Frame<Real> &F, const Real *lc, Real x0) {
+    using PL = Planar<T>;
+    constexpr unsigned ZW = PL::ZW, ZV = PL::ZV;
+    Real oB[3], vB[3], t[3], t2[3];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) F.R[i] = lc[i];
+    oB[0] = lc[9] - x0; oB[1] = lc[10]; oB[2] = lc[11];
+    const Real *wrg = lc + 12, *vrel = lc + 15, *al = lc + 18, *aa = lc + 21;
+    cross3m<ZW, 0>(wrg, oB, t);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { F.o[i] = oB[i]; F.w[i] = wrg[i]; F.vO[i] = vrel[i] - t[i]; F.al[i] = al[i]; }
+    cross3m<ZW, 0>(F.w, oB, t);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) vB[i] = F.vO[i] + t[i];
+    cross3m<ZW, 0>(al, oB, t);
+    cross3m<ZW, ZV>(F.w, vB, t2);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) F.aO[i] = aa[i] - t[i] - t2[i];
+    PL::rot(F.R); PL::ang(F.w); PL::lin(F.vO); PL::ang(F.al); PL::lin(F.aO);
+}
+
 /* identity joint (LOC slot NB) and the ground frame (KB/AL slot NB) */
 /* BIOIM_GROUND_ONCE (the step kernels): the ground slot's constants — the KB
  * rotation, its zero origin / velocity words and the zero AL row, which no
@@ -1122,10 +1292,9 @@ template <class T, typename Real, bool ONCE = false> DEV void kin_ground(Real *l
 /* Phase 1b (lane = body c): compose c's root-to-body joint chain in
  * registers (front-padded with the identity joint, so every lane runs the
  * same DEPTH compositions with no inter-lane dependency) */
-template <class T, typename Real>
-DEV void kin_chain(const SModel<T, Real> &SM, Real *lds, int c, Real x0) {
+template <class T, typename Real, int FE = 0>
+DEV void kin_chain(const SModel<T, Real> &SM, Real *lds, int c, Real x0, Frame<Real> &F) {
     using LY = Lay<T, Real>;
-    Frame<Real> F;
 #pragma unroll
     for (int i = 0; i < 9; ++i) F.R[i] = (i % 4) == 0 ? Real(1) : Real(0);
 #pragma unroll
@@ -1137,7 +1306,8 @@ DEV void kin_chain(const SModel<T, Real> &SM, Real *lds, int c, Real x0) {
 #pragma unroll
         for (int i = 0; i < 24; ++i) lc[i] = src[i];
         Planar<T>::loc(lc);
-        compose<T, Real>(F, lc);
+        if constexpr (lvl == 0 && (FE & FE_LEVEL0) != 0) compose_ground<T, Real>(F, lc, x0);
+        else compose<T, Real>(F, lc);
     });
     Real *kb = lds + LY::KB + 18 * c, *ab = lds + LY::AL + 6 * c;
 #pragma unroll
@@ -1147,6 +1317,11 @@ DEV void kin_chain(const SModel<T, Real> &SM, Real *lds, int c, Real x0) {
         kb[9 + i] = F.o[i]; kb[12 + i] = F.w[i]; kb[15 + i] = F.vO[i];
         ab[i] = F.al[i]; ab[3 + i] = F.aO[i];
     }
+}
+template <class T, typename Real>
+DEV void kin_chain(const SModel<T, Real> &SM, Real *lds, int c, Real x0) {
+    Frame<Real> F;
+    kin_chain<T, Real>(SM, lds, c, x0, F);
 }
 
 /* Phase 0b: the function slots (Lay::MF), one lane each — moving path
@@ -1195,18 +1370,28 @@ DEV void kin_column(const SModel<T, Real> &SM, Real *lds, int d) {
 
 /* Phase 1c (lane = body): spatial inertia at the ground origin and the
  * Newton-Euler (velocity-product + gravity) wrench */
-template <class T, typename Real>
-DEV void body_inertia(const SModel<T, Real> &SM, const DModel<Real> &M, Real *lds, int c) {
+template <class T, typename Real, bool FROM_FRAME = false>
+DEV void body_inertia(const SModel<T, Real> &SM, const DModel<Real> &M, Real *lds, int c, const Frame<Real> *F = nullptr) {
     using LY = Lay<T, Real>;
     using PL = Planar<T>;
     constexpr unsigned ZR = PL::ZR, ZW = PL::ZW, ZV = PL::ZV;
     const SBody<Real> &b = SM.body[c];
     const Real *kb = lds + LY::KB + 18 * c, *ab = lds + LY::AL + 6 * c;
     Real K[18], A[6];
+    if constexpr (FROM_FRAME) {   /* FE_INERTIA: the frame kin_chain left in the lane's registers */
 #pragma unroll
-    for (int i = 0; i < 18; ++i) K[i] = kb[i];
+        for (int i = 0; i < 9; ++i) K[i] = F->R[i];
 #pragma unroll
-    for (int i = 0; i < 6; ++i) A[i] = ab[i];
+        for (int i = 0; i < 3; ++i) {
+            K[9 + i] = F->o[i]; K[12 + i] = F->w[i]; K[15 + i] = F->vO[i];
+            A[i] = F->al[i]; A[3 + i] = F->aO[i];
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 18; ++i) K[i] = kb[i];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) A[i] = ab[i];
+    }
     PL::frame(K); PL::acc(A);
     const Real *R = K, *o = K + 9, *w = K + 12, *vO = K + 15, *al = A, *aO = A + 3;
     Real cl[3], cG[3];
@@ -1893,6 +2078,8 @@ template <class T, bool IMP = true> struct BfSwitch {
 template <class T, bool FUSED = false> struct TailSwitch {
     static constexpr int BIT = FUSED ? 4 : (T::PLANAR ? 1 : 2);
     static constexpr bool GROUND = (BIOIM_GROUND_ONCE & BIT) != 0;
+    /* the family's BIOIM_FRONTEND byte (FE_* bits) */
+    static constexpr int FE = (BIOIM_FRONTEND >> (FUSED ? 16 : (T::PLANAR ? 0 : 8))) & 0xFF;
 };
 template <class T, typename Real, bool PERT, bool BF_ROWS, bool IMP, bool CACHE = false, class TS = TailSwitch<T>>
 DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Real ud,
@@ -1965,10 +2152,13 @@ DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Rea
         }
         wave_sync();
     } else {
+    constexpr int FE = TS::FE;
     publish_coords<T, Real>(M, SM, lds, lane, qd, ud);
-    if (lane < ND) {
+    if constexpr (!(FE & FE_COLS)) {   /* FE_COLS: kin_local stores every dof's SL row whole */
+        if (lane < ND) {
 #pragma unroll
-        for (int i = 0; i < 6; ++i) lds[LY::SL + 6 * lane + i] = 0;
+            for (int i = 0; i < 6; ++i) lds[LY::SL + 6 * lane + i] = 0;
+        }
     }
     wave_sync();
     Real x0 = 0;
@@ -1984,18 +2174,14 @@ DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Rea
     STAMP(15);
 
     /* ---- phase 1: lane-parallel kinematics */
-    if (lane < NB) kin_local<T, Real>(SM, lds, lane);
+    if (lane < NB) kin_local<T, Real, FE>(SM, lds, lane);
     if (lane == NB) kin_ground<T, Real, TS::GROUND>(lds, x0);
     wave_sync();
     STAMP(0);
-    if (lane < NB) kin_chain<T, Real>(SM, lds, lane, x0);
-    wave_sync();
-    STAMP(1);
-    if (lane < ND) kin_column<T, Real>(SM, lds, lane);
-    if (lane < NB) {
-        body_inertia<T, Real>(SM, M, lds, lane);
-        /* apply_perturbations: ground-frame force (fx, 0, 0) at the origin of
-         * OpenSim body P.ob (the torso), muscle_walking_imitation_env2D.py:83-100 */
+    /* apply_perturbations: ground-frame force (fx, 0, 0) at the origin of
+     * OpenSim body P.ob (the torso), muscle_walking_imitation_env2D.py:83-100
+     * (the body's own lane: it reads back the frame and wrench it stored) */
+    auto push = [&]() {
         if (PERT && lane == SM.os_cb[P.ob]) {
             const Real fpx = pert_force<Real>(P, pslot, pk);
             const Real *kb = lds + LY::KB + 18 * lane;
@@ -2006,8 +2192,34 @@ DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Rea
             wb[2] += (p[1] + kb[10]) * fpx;
             wb[3] -= fpx;
         }
+    };
+    if constexpr ((FE & FE_INERTIA) != 0) {
+        /* the body lane goes from its chain to its inertia and wrench with the
+         * frame in registers; the columns (which read the parents' frames)
+         * then run with the subtree sums' reads below, after one sync */
+        if (lane < NB) {
+            Frame<Real> F;
+            kin_chain<T, Real, FE>(SM, lds, lane, x0, F);
+            body_inertia<T, Real, true>(SM, M, lds, lane, &F);
+            push();
+        }
+        wave_sync();
+        STAMP(1);
+        if (lane < ND) kin_column<T, Real>(SM, lds, lane);
+    } else {
+        if (lane < NB) {
+            Frame<Real> F;
+            kin_chain<T, Real, FE>(SM, lds, lane, x0, F);
+        }
+        wave_sync();
+        STAMP(1);
+        if (lane < ND) kin_column<T, Real>(SM, lds, lane);
+        if (lane < NB) {
+            body_inertia<T, Real>(SM, M, lds, lane);
+            push();
+        }
+        wave_sync();
     }
-    wave_sync();
     STAMP(2);
 
     /* ---- phase 2: lane-parallel force elements */
@@ -4796,7 +5008,7 @@ DEV void env_block(const LaunchArgs<T, Real> &a, int blk) {
     __syncthreads();
 #ifdef BIOIM_STAMPS
     const unsigned long long k_t1 = __builtin_amdgcn_s_memtime();
-    if (blockIdx.x == 0 && threadIdx.x == 0) g_stamps[11] += k_t1 - k_t0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) { g_stamps[11] += k_t1 - k_t0; g_stamps[26] = 1 + TS::FE; }   /* 26: the kernel's front-end bits + 1 (tools/stamps.py names slots 1-2 by FE_INERTIA) */
 #endif
     const SModel<T, Real> &SM = *reinterpret_cast<const SModel<T, Real> *>(smem_raw);
     const DModel<Real> &M = *Mg;

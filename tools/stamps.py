@@ -32,12 +32,18 @@ for k in range(steps):
     env.step(acts[5 + k])
 torch.cuda.synchronize()
 f(buf, 1)
-names = ['kin local (after slots)', 'kin compose (levels)', 'columns + inertias', 'subtree sums', 'muscle path',
+# slots 1-2 by the kernel's own front-end bits (slot 26 = 1 + TailSwitch::FE; 0: a build from before
+# BIOIM_FRONTEND).  With FE_INERTIA (4) the body lane goes from its chain to its inertia and wrench before the
+# sync and the columns stand alone; without it the inertias are in slot 2 with the columns.
+fe = int(buf[26]) - 1 if buf[26] else 0
+inertia_early = bool(fe & 4)
+names = ['kin local (after slots)', 'kin compose (levels) + inertias' if inertia_early else 'kin compose (levels)',
+         'columns' if inertia_early else 'columns + inertias', 'subtree sums', 'muscle path',
          'muscle eval / actuators', 'contacts', 'limits + sync', 'M entries + rhs', 'cholesky']
 tot = sum(buf[i] for i in range(len(names))) + buf[15]
 print(f'  publish + function slots (phase 0/0b) {buf[15] / (steps * (env.nsub + 1)):9.0f} cyc  {100.0 * buf[15] / tot:5.1f} %')
 calls = steps * (env.nsub + 1)
-print(f'{env_id} fp{prec}: cycles per dynamics call {tot / calls:.0f} (workgroup 0, env 0)')
+print(f'{env_id} fp{prec}: cycles per dynamics call {tot / calls:.0f} (workgroup 0, env 0; front-end bits {fe:#04x})')
 for i, n in enumerate(names):
     print(f'  {n:32s} {buf[i] / calls:9.0f} cyc  {100.0 * buf[i] / tot:5.1f} %')
 print(f'  per launch: loop {buf[10] / steps:.0f} cyc, of which dynamics {tot / steps:.0f}; '
