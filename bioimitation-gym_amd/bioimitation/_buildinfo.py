@@ -17,7 +17,14 @@ PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REPO = os.path.dirname(PKG_ROOT)
 CSRC = os.path.join(PKG_ROOT, 'csrc')
 INCLUDE = os.path.join(REPO, 'include')
-SOURCES = [os.path.join(CSRC, f) for f in ('bioim_step.hip', 'bioim_device.h', 'topologies.h')] + \
+# bioim_step.hip is the one file handed to the compiler; the headers it
+# includes hold its lowest layers (DESIGN.md 5.6 has the map).  Every one is listed by
+# name: a header missing here would leave the build id, and so a stale library,
+# unchanged when it is edited (tests/test_abi.py follows the #include lines
+# and checks this list against them).
+SOURCES = [os.path.join(CSRC, f) for f in (
+    'bioim_step.hip', 'bioim_device.h', 'topologies.h',
+    'bioim_config.h', 'bioim_math.h', 'bioim_diag.h', 'bioim_layout.h')] + \
     [os.path.join(INCLUDE, f) for f in ('bioim.h', 'bioim_modelpack.h')] + \
     [os.path.join(REPO, '__graft_entry__.py')]   # the per-object -D unit selectors and the link line live there
 
@@ -43,8 +50,8 @@ def sources_present():
 
 
 def build_id(extra=()):
-    """sha256 over the kernel sources, the build recipe and the compile
-    flags, 16 hex digits."""
+    """sha256 over the kernel sources (bioim_step.hip and every header it
+    includes: SOURCES), the build recipe and the compile flags, 16 hex digits."""
     h = hashlib.sha256()
     for f in SOURCES:
         h.update(os.path.basename(f).encode())

@@ -40,272 +40,12 @@
 #include "bioim_device.h"
 #include "topologies.h"
 
-#define DEV __device__ __forceinline__
-#define BIOIM_EPB 16 /* envs per workgroup (BIOIM_EPB * G threads) share one LDS model image */
-/* env flags baked into a kernel (topologies.h FLAGS); RAW_ACTION, TARGET_OBS, GRF_OBS are run-time */
-#define BIOIM_STRUCT_FLAGS (BIOIM_ENV_MUSCLE | BIOIM_ENV_HAS_TZ | BIOIM_ENV_REWARD_FEET | BIOIM_ENV_DONE_CROSS | BIOIM_ENV_PD)
-
-#ifndef BIOIM_CHECK
-#define BIOIM_CHECK 0
-#endif
-/* BIOIM_CHECK=1 (a diagnostic build, never shipped): every global load and
- * store of the env kernel goes through a bounds check that prints the source
- * line, the index, the bound, the workgroup and the thread, then traps — the
- * stale-lane class of DESIGN.md 5.5 then ends as a named trap instead of an
- * anonymous illegal-address fault.  With BIOIM_CHECK=0 the accessors expand to
- * plain subscripts (the shipped kernels are unchanged). */
-DEV size_t bioim_chk(size_t i, size_t n, int line) {
-    if (i >= n) {
-        printf("BIOIM_CHECK bioim_step.hip:%d index %llu outside [0, %llu) workgroup %u thread %u\n", line,
-               (unsigned long long)i, (unsigned long long)n, blockIdx.x, threadIdx.x);
-        __builtin_trap();
-    }
-    return i;
-}
-#if BIOIM_CHECK
-#define GAT(p, i, n) ((p)[bioim_chk((size_t)(i), (size_t)(n), __LINE__)])
-#define GIDX(i, n) bioim_chk((size_t)(i), (size_t)(n), __LINE__)
-#else
-#define GAT(p, i, n) ((p)[i])
-#define GIDX(i, n) (i)
-#endif
-
-template <int I, int N, class F>
-DEV void sfor(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        sfor<I + 1, N>(f);
-    }
-}
-
-#ifndef BIOIM_ENV_MOD
-#define BIOIM_ENV_MOD -1
-#endif
-#ifndef BIOIM_BF3
-#define BIOIM_BF3 122
-#endif
-#ifndef BIOIM_BF_SPATIAL
-#define BIOIM_BF_SPATIAL 0
-#endif
-/* BIOIM_BF3_RK=1 (shipped): the BIOIM_BF3 pieces in the spatial RK-Merson
- * kernels too — no scratch, hazard gate clean, same-box Running3D RK launch
- * 0.7826 -> 0.7452 ms, LockedKnee3D 0.7289 -> 0.6989 ms (profiles/r04/r04g/ab_rk.log) */
-#ifndef BIOIM_BF3_RK
-#define BIOIM_BF3_RK 1
-#endif
-/* fiber-velocity warm start (round-5 experiments): BIOIM_FV_HERMITE = cubic
- * Hermite u(v) start from the table slopes instead of linear interpolation;
- * BIOIM_FV_PRED = linear extrapolation of the previous two substeps' roots
- * in the semi-implicit substep loop */
-#ifndef BIOIM_FV_HERMITE
-#define BIOIM_FV_HERMITE 0
-#endif
-#ifndef BIOIM_FV_PRED
-#define BIOIM_FV_PRED 0
-#endif
-/* the substep's fiber-length update through fast_rcp instead of the IEEE
- * division (round-5 experiment, off: the oracle divides, and after 6 steps
- * the realize report drifted to 1.4e-9 of it, past the 1e-9 report test,
- * profiles/r05/r05p/gpu_tests.log) */
-#ifndef BIOIM_SUBSTEP_RCP
-#define BIOIM_SUBSTEP_RCP 0
-#endif
-/* BIOIM_SGB: sched_group_barrier pipelines in the muscle eval (round-5
- * experiment, off; same box C3 +1.3 % / +1.8 %: profiles/r05/r05o) */
-#ifndef BIOIM_SGB
-#define BIOIM_SGB 0
-#endif
-/* solve_fv: a lane whose root lies past the curve's end leaves the Newton
- * loop after one step (0: it iterates to the segment end as before) */
-#ifndef BIOIM_FV_PAST_END
-#define BIOIM_FV_PAST_END 1
-#endif
-#ifndef BIOIM_FV_PE_PLANAR
-#define BIOIM_FV_PE_PLANAR 0
-#endif
-/* the reset table (LaunchArgs::reset_tab) in the planar RK-Merson step
- * kernels too, and (round 6) in the spatial ones: they fit it at 486-512
- * registers with no scratch; same-box reference-integrator legs C4 +3.9 %,
- * LockedKnee3D +4.4 %, Palsy3D +5.6 % (profiles/r06/r06e/ab_rk.txt) */
-#ifndef BIOIM_RESET_TAB_RK_SPATIAL
-#define BIOIM_RESET_TAB_RK_SPATIAL 1
-#endif
-#ifndef BIOIM_RESET_TAB_RK
-#define BIOIM_RESET_TAB_RK 1
-#endif
-template <typename Real> struct Eps;
-template <> struct Eps<float> {
-    static constexpr float u_tol = 2e-7f;   /* Bezier parameter tolerance  */
-    static constexpr float u_stop = 2e-7f;  /* Newton step after which the root is converged */
-    static constexpr float v_tol = 1e-7f;   /* normalized velocity         */
-    static constexpr float l_tol = 1e-9f;   /* fiber length (m)            */
-    static constexpr float l_stop = 1e-9f;  /* Newton step after which the length is converged */
-    static constexpr float h_stop = 0.0f;   /* fiber-equilibrium residual stop (off in fp32) */
-    static constexpr int it_max = 24;
-    static constexpr int curve_newton = 1; /* from the Hermite start: 5.9e-9 < fp32 rounding */
-};
-template <> struct Eps<double> {
-    static constexpr double u_tol = 1e-15;
-    /* a Newton step of at most 1e-11 leaves an error ~ |g''/2g'| 1e-22 in u
-     * (quadratic convergence; the smooth curves have |g''/g'| = O(10)) */
-    static constexpr double u_stop = 1e-11;
-    static constexpr double v_tol = 1e-15;
-    static constexpr double l_tol = 1e-15;
-    static constexpr double l_stop = 1e-10;
-    /* the oracle's residual stop of the reset fiber equilibrium
-     * (oracle/bioim_oracle.c muscle_equilibrium, |H| < 1e-12): where the root is
-     * ill-conditioned (a tendon at its slack length: H nearly flat in l) the
-     * iterate that stop returns is the oracle's, instead of one converged
-     * further (round 6: Palsy3D tib_ant_r at reset row 46, 9.2e-12 apart;
-     * DESIGN.md 2) */
-    static constexpr double h_stop = 1e-12;
-    static constexpr int it_max = 60;
-    static constexpr int curve_newton = 2; /* from the Hermite start: 8.9e-16 */
-};
-
-/* ------------------------------------------------------------- vec3 */
-template <typename Real> DEV void cross3(const Real *a, const Real *b, Real *o) {
-    Real x = a[1] * b[2] - a[2] * b[1], y = a[2] * b[0] - a[0] * b[2], z = a[0] * b[1] - a[1] * b[0];
-    o[0] = x; o[1] = y; o[2] = z;
-}
-template <typename Real> DEV Real dot3(const Real *a, const Real *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-template <typename Real> DEV void mv3(const Real *R, const Real *v, Real *o) {
-    Real x = R[0] * v[0] + R[1] * v[1] + R[2] * v[2];
-    Real y = R[3] * v[0] + R[4] * v[1] + R[5] * v[2];
-    Real z = R[6] * v[0] + R[7] * v[1] + R[8] * v[2];
-    o[0] = x; o[1] = y; o[2] = z;
-}
-template <typename Real> DEV void mm3(const Real *A, const Real *B, Real *C) {
-    Real T[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) T[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) C[i] = T[i];
-}
-/* The same products with compile-time zero masks (bit i: operand entry i
- * is known to be zero): a term with a known-zero factor is left out, so
- * planar models (Planar below) run the 2-D arithmetic through the same
- * code; with empty masks these are exactly mv3 / mm3 / cross3 / dot3
- * (same terms, same order). */
-template <unsigned ZA, unsigned ZB, int N, typename Real>
-DEV Real sum_m(const Real *a, const Real *b, const int (&ia)[N], const int (&ib)[N], const int (&sg)[N]) {
-    Real acc = 0;
-    bool first = true;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        if (((ZA >> ia[k]) & 1u) || ((ZB >> ib[k]) & 1u)) continue;
-        const Real t = a[ia[k]] * b[ib[k]];
-        acc = first ? (sg[k] > 0 ? t : -t) : (sg[k] > 0 ? acc + t : acc - t);
-        first = false;
-    }
-    return acc;
-}
-template <unsigned ZA, unsigned ZB, typename Real> DEV void mv3m(const Real *R, const Real *v, Real *o) {
-    Real r[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const int ia[3] = {3 * i, 3 * i + 1, 3 * i + 2}, ib[3] = {0, 1, 2}, sg[3] = {1, 1, 1};
-        r[i] = sum_m<ZA, ZB, 3>(R, v, ia, ib, sg);
-    }
-    o[0] = r[0]; o[1] = r[1]; o[2] = r[2];
-}
-template <unsigned ZA, unsigned ZB, typename Real> DEV void mm3m(const Real *A, const Real *B, Real *C) {
-    Real T[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int ia[3] = {3 * i, 3 * i + 1, 3 * i + 2}, ib[3] = {j, 3 + j, 6 + j}, sg[3] = {1, 1, 1};
-            T[3 * i + j] = sum_m<ZA, ZB, 3>(A, B, ia, ib, sg);
-        }
-#pragma unroll
-    for (int i = 0; i < 9; ++i) C[i] = T[i];
-}
-template <unsigned ZA, unsigned ZB, typename Real> DEV void cross3m(const Real *a, const Real *b, Real *o) {
-    const int sg[2] = {1, -1};
-    const int ia0[2] = {1, 2}, ib0[2] = {2, 1}, ia1[2] = {2, 0}, ib1[2] = {0, 2}, ia2[2] = {0, 1}, ib2[2] = {1, 0};
-    Real x = sum_m<ZA, ZB, 2>(a, b, ia0, ib0, sg), y = sum_m<ZA, ZB, 2>(a, b, ia1, ib1, sg),
-         z = sum_m<ZA, ZB, 2>(a, b, ia2, ib2, sg);
-    o[0] = x; o[1] = y; o[2] = z;
-}
-template <unsigned ZA, unsigned ZB, typename Real> DEV Real dot3m(const Real *a, const Real *b) {
-    const int ia[3] = {0, 1, 2}, sg[3] = {1, 1, 1};
-    return sum_m<ZA, ZB, 3>(a, b, ia, ia, sg);
-}
-
-/* Planar topologies (T::PLANAR; the host checks each pack, pack_is_planar):
- * frames rotate about z only, so R13 = R23 = R31 = R32 = 0 and R33 = 1,
- * angular velocities and accelerations lie along z, linear ones in the x-y
- * plane.  These helpers write those zeros over values just read from LDS;
- * in the functions that use them the products with the known zeros then fold
- * away (those functions are compiled without signed zeros / NaN semantics:
- * `#pragma float_control(precise, off)`), so a planar model runs 2-D
- * arithmetic through the same source.  No-ops for spatial topologies. */
-template <class T> struct Planar {
-    /* zero masks (mv3m / mm3m / cross3m / dot3m): rotation, angular, linear */
-    static constexpr unsigned ZR = T::PLANAR ? 0xE4u : 0u, ZW = T::PLANAR ? 0x3u : 0u, ZV = T::PLANAR ? 0x4u : 0u;
-    template <typename Real> static DEV void rot(Real *R) {
-        if constexpr (T::PLANAR) { R[2] = R[5] = R[6] = R[7] = Real(0); R[8] = Real(1); }
-    }
-    template <typename Real> static DEV void ang(Real *w) {
-        if constexpr (T::PLANAR) { w[0] = w[1] = Real(0); }
-    }
-    template <typename Real> static DEV void lin(Real *v) {
-        if constexpr (T::PLANAR) { v[2] = Real(0); }
-    }
-    /* frame slot KB: R9 o3 w3 vO3 */
-    template <typename Real> static DEV void frame(Real *kb) { rot(kb); ang(kb + 12); lin(kb + 15); }
-    /* joint-local slot LOC: R9 p3 wrel3 vrel3 arel3 aa3 */
-    template <typename Real> static DEV void loc(Real *lc) { rot(lc); ang(lc + 12); lin(lc + 15); ang(lc + 18); lin(lc + 21); }
-    /* acceleration slot AL: alpha3 aO3 */
-    template <typename Real> static DEV void acc(Real *ab) { ang(ab); lin(ab + 3); }
-    /* Plucker column: Omega3 V3 */
-    template <typename Real> static DEV void col(Real *s) { ang(s); lin(s + 3); }
-};
-
-DEV void sincos_rt(double x, double &s, double &c);
-DEV void sincos_rt(float x, float &s, float &c);
-template <typename Real> DEV void axis_rot(const Real *a, Real th, Real *R) {
-    Real s, c;
-    sincos_rt(th, s, c);
-    Real t = Real(1) - c, x = a[0], y = a[1], z = a[2];
-    R[0] = t * x * x + c;     R[1] = t * x * y - s * z; R[2] = t * x * z + s * y;
-    R[3] = t * x * y + s * z; R[4] = t * y * y + c;     R[5] = t * y * z - s * x;
-    R[6] = t * x * z - s * y; R[7] = t * y * z + s * x; R[8] = t * z * z + c;
-}
-
-template <int G, typename Real> DEV Real group_sum(Real x) {
-#pragma unroll
-    for (int off = G / 2; off >= 1; off >>= 1) x += __shfl_xor(x, off, G);
-    return x;
-}
-template <int G, typename Real> DEV Real group_max(Real x) {
-#pragma unroll
-    for (int off = G / 2; off >= 1; off >>= 1) x = fmax(x, __shfl_xor(x, off, G));
-    return x;
-}
-template <int G> DEV bool group_any(bool p) {
-    unsigned long long b = __ballot(p);
-    int base = (threadIdx.x & 63) & ~(G - 1);
-    unsigned long long m = (G == 64) ? ~0ull : ((1ull << G) - 1ull);
-    return ((b >> base) & m) != 0ull;
-}
-
-#ifdef BIOIM_STAMPS
-__device__ unsigned long long g_stamps[28];
-#endif
-/* Diagnostic build only (-DBIOIM_WAVETIME, single translation unit,
- * tools/wavetime.py): shader cycles of every wave of the last step launch */
-#ifdef BIOIM_WAVETIME
-#define BIOIM_WAVETIME_N 65536
-__device__ unsigned long long g_wavetime[BIOIM_WAVETIME_N];
-/* per thread of the last launch: fiber-velocity Newton iterations (sum over
- * the launch's solves), the most of one solve, bisection fallbacks */
-__device__ unsigned g_fvit[BIOIM_WAVETIME_N * 4], g_fvmax[BIOIM_WAVETIME_N * 4], g_fvbis[BIOIM_WAVETIME_N * 4];
-DEV unsigned diag_tid() { return blockIdx.x * blockDim.x + threadIdx.x; }
-#endif
+// The lowest layers, lowest first (DESIGN.md 5.6 has the map); each header
+// includes what it uses.
+#include "bioim_config.h"
+#include "bioim_math.h"
+#include "bioim_diag.h"
+#include "bioim_layout.h"
 
 /* ------------------------------------------------------------ functions */
 template <class T, typename Real>
@@ -418,95 +158,7 @@ DEV void fn_eval_km(const SModel<T, Real> &SM, int fi, Real q, Real &f, Real &f1
     f = present ? v : Real(0); f1 = present ? v1 : Real(0); f2 = present ? v2 : Real(0);
 }
 
-/* sin and cos with one shared range reduction.  fp64: Cody-Waite reduction
- * by pi/2 (three-part constant, exact for |x| < 1e5, far beyond joint
- * angles) and Taylor polynomials on [-pi/4, pi/4] (truncation < 1e-19);
- * agrees with libm to ~1 ulp.  fp32: the device sincosf. */
-DEV void sincos_rt(double x, double &s, double &c) {
-    const double k = rint(x * 0.63661977236758134308);
-    double r = fma(-k, 1.57079632679489655800e+00, x);
-    r = fma(-k, 6.12323399573676603587e-17, r);
-    r = fma(-k, -1.4973849048591698e-33, r);
-    const double r2 = r * r;
-    double ps = 2.8114572543455208e-15;                /* 1/17! */
-    ps = fma(ps, r2, -7.6471637318198164e-13);         /* -1/15! */
-    ps = fma(ps, r2, 1.6059043836821613e-10);          /* 1/13! */
-    ps = fma(ps, r2, -2.5052108385441720e-08);         /* -1/11! */
-    ps = fma(ps, r2, 2.7557319223985893e-06);          /* 1/9! */
-    ps = fma(ps, r2, -1.9841269841269841e-04);         /* -1/7! */
-    ps = fma(ps, r2, 8.3333333333333333e-03);          /* 1/5! */
-    ps = fma(ps, r2, -1.6666666666666667e-01);         /* -1/3! */
-    const double sr = fma(ps * r2, r, r);
-    double pc = 1.5619206968586225e-16;                /* 1/18! */
-    pc = fma(pc, r2, -4.7794773323873853e-14);         /* -1/16! */
-    pc = fma(pc, r2, 1.1470745597729725e-11);          /* 1/14! */
-    pc = fma(pc, r2, -2.0876756987868099e-09);         /* -1/12! */
-    pc = fma(pc, r2, 2.7557319223985891e-07);          /* 1/10! */
-    pc = fma(pc, r2, -2.4801587301587302e-05);         /* -1/8! */
-    pc = fma(pc, r2, 1.3888888888888889e-03);          /* 1/6! */
-    pc = fma(pc, r2, -4.1666666666666667e-02);         /* -1/4! */
-    pc = fma(pc, r2, 0.5);
-    const double cr = fma(-pc, r2, 1.0);
-    const int q = (int)k & 3;
-    const double ss = (q & 1) ? cr : sr, cc = (q & 1) ? sr : cr;
-    s = (q & 2) ? -ss : ss;
-    c = ((q + 1) & 2) ? -cc : cc;
-}
-DEV void sincos_rt(float x, float &s, float &c) { sincosf(x, &s, &c); }
-
 /* ----------------------------------------------------- smooth curves */
-/* BIOIM_EXACT_RCP=1: a diagnostic build (never shipped) whose reciprocals
- * and inverse square roots below are IEEE divisions and square roots, the
- * oracle's operations — to attribute the GPU's operation-level distance from
- * the oracle */
-#ifndef BIOIM_EXACT_RCP
-#define BIOIM_EXACT_RCP 0
-#endif
-#if BIOIM_EXACT_RCP
-DEV double newton_rcp(double x) { return 1.0 / x; }
-DEV float newton_rcp(float x) { return 1.0f / x; }
-DEV double fast_rcp(double x) { return 1.0 / x; }
-DEV float fast_rcp(float x) { return 1.0f / x; }
-DEV double fast_rsqrt(double x) { return 1.0 / sqrt(x); }
-DEV float fast_rsqrt(float x) { return 1.0f / sqrtf(x); }
-#else
-/* reciprocal for Newton updates (a self-correcting iteration tolerates a
- * last-bits error in the step): hardware rcp plus one refinement */
-DEV double newton_rcp(double x) {
-    double r = __builtin_amdgcn_rcp(x);
-    const double e = fma(-x, r, 1.0);
-    return fma(r, e, r);
-}
-DEV float newton_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-/* reciprocal to (about) the last bit: hardware rcp plus two refinements —
- * a shorter dependency chain than the IEEE division sequence; used where the
- * divisor is a well-scaled positive quantity (lengths, cosines, time
- * constants, slip speeds) */
-DEV double fast_rcp(double x) {
-    double r = __builtin_amdgcn_rcp(x);
-    double e = fma(-x, r, 1.0);
-    r = fma(r, e, r);
-    e = fma(-x, r, 1.0);
-    return fma(r, e, r);
-}
-DEV float fast_rcp(float x) {
-    float r = __builtin_amdgcn_rcpf(x);
-    return fmaf(r, fmaf(-x, r, 1.0f), r);
-}
-/* 1/sqrt(x) for x > 0: hardware rsq plus two Newton refinements; a length
- * and its inverse then cost one rsq (len = x * rsqrt(x)) instead of an IEEE
- * sqrt and a reciprocal */
-DEV double fast_rsqrt(double x) {
-    double y = __builtin_amdgcn_rsq(x);
-    const double hx = 0.5 * x;
-    y = fma(y, fma(-hx * y, y, 0.5), y);
-    return fma(y, fma(-hx * y, y, 0.5), y);
-}
-DEV float fast_rsqrt(float x) {
-    float y = __builtin_amdgcn_rsqf(x);
-    return fmaf(y, fmaf(-0.5f * x * y, y, 0.5f), y);
-}
-#endif
 
 /* a quintic segment in the power basis c[0] + c[1] u + ... + c[5] u^5
  * (converted from the Bezier control points at create time, convert_curve):
@@ -687,147 +339,6 @@ DEV void solve_fv(const DCurve<Real> &C, Real afal, Real beta, Real rhs, Real v0
     }
 }
 
-/* muscle of lane slot s (slot = lane + j * G): when the muscles take two
- * passes over the lanes, the second, partly idle pass holds the cheapest
- * paths (T::mperm, tools/build_packs.py); a bijection of [0, NM), the
- * identity elsewhere, so slot-range checks stay valid */
-template <class T> DEV int mslot(int s) {
-    int r = s;
-    if constexpr (T::NM > T::G) {
-        sfor<0, T::NM>([&](auto iI) {
-            constexpr int i = decltype(iI)::value;
-            r = s == i ? T::mperm[i] : r;
-        });
-    }
-    return r;
-}
-
-/* ---------------------------------------------------------- LDS layout
- * Per workgroup: the shared model image (SModel, bioim_device.h), then one
- * region per env.  Phase 1 (lane-parallel kinematics) publishes frames,
- * Plucker columns, per-body inertias and Newton-Euler wrenches; the force
- * phases read them and publish per-lane slots that are reduced in a fixed
- * order (bitwise deterministic).  The union region U is reused by phase 1
- * (joint-local data), phases 2-3 (force slots) and the observation staging. */
-template <class T, typename Real> struct Lay {
-    static constexpr int NB = T::NB, ND = T::ND > 0 ? T::ND : 1, NC = T::NC, NP = ND * (ND + 1) / 2;
-    static constexpr int NMS = T::NM > T::NA ? T::NM : T::NA;
-    static constexpr int MPL = (NMS + T::G - 1) / T::G;      /* muscles (actions) per lane            */
-    static constexpr int NS = T::NS > 0 ? T::NS : 1, NL = T::NL > 0 ? T::NL : 1;
-    static constexpr int CJN = 10;               /* per sphere: P3, F3 (implicit), C4 (xx xz yy zz)  */
-    static constexpr int NTR = (T::TX >= 0) + (T::TY >= 0) + (T::TZ >= 0);
-    /* largest observation of the topology (target obs and GRF on) */
-    static constexpr int OBSMAX = 1 + (NC - NTR) + 2 * NC + 2 * (NC - 1) + 3 * (T::NOBP + T::NOBV) + 3 * T::NM +
-                                  6 * T::NF;
-    static constexpr int KB = 0;                 /* [NB+1][18]: R9 o3 w3 vO3 (slot NB: ground)      */
-    static constexpr int AL = KB + 18 * (NB + 1); /* [NB+1][6]: alpha3, aO3 (velocity-product accels) */
-    static constexpr int S = AL + 6 * (NB + 1);  /* [ND][6]: Plucker columns (Omega, V at origin)   */
-    static constexpr int QF = S + 6 * ND;        /* [NC] coordinate values                          */
-    static constexpr int UF = QF + NC;           /* [NC] coordinate speeds                          */
-    static constexpr int IC = UF + NC;           /* [NB][10]: m, h3, J6; then in place: subtree sums */
-    static constexpr int WB = IC + 10 * NB;      /* [NB][6]: n3, f3; then in place: subtree sums     */
-    static constexpr int MP = WB + 6 * NB;       /* [NP] packed lower M (+implicit)                 */
-    static constexpr int RHS = MP + NP;          /* [ND]                                            */
-    static constexpr int CW = RHS + ND;          /* [NS][8]: F3, Mo3, active                        */
-    static constexpr int LIM = CW + 8 * NS;      /* [NL][4]: f, diag add, tau add                   */
-    static constexpr int NSLOT = TopoInfo<T>::nslot();
-    static constexpr int MF = LIM + 4 * NL;      /* [NSLOT][3]: function slots f, f', f''           */
-    static constexpr int U = ((MF + 3 * (NSLOT > 0 ? NSLOT : 1) + 1) / 2) * 2;
-    static constexpr int LOC = U;                /* phase 1: [NB+1][24] joint-local data (NB: identity) */
-    static constexpr int SL = LOC + 24 * (NB + 1); /* phase 1: [ND][6] joint-local Plucker columns, + sink row */
-    /* phases 2-3: [MPL * G][MAXSPAN] per muscle slot, -F_t dL/dq over its
-     * span (actuator slot: its torque), then one zero slot (TZ) */
-    static constexpr int TZ = MPL * T::G * T::MAXSPAN;
-    static constexpr int TAUN = TZ + 1;
-    static constexpr int TAU = U;
-    static constexpr int CJ = TAU + TAUN;        /* phases 2-3: [NS][CJN] contact slots             */
-    static constexpr int OBS = U;                /* report: observation staging                     */
-    static constexpr int REP = OBS + OBSMAX;     /* report: [NOS+1][6] body pos/vel (NOS: COM)      */
-    static constexpr int U1 = 24 * (NB + 1) + 6 * (ND + 1), U2 = TAUN + NS * CJN;
-    static constexpr int U3 = OBSMAX + 6 * (T::NOS + 1);
-    static constexpr int USZ = U1 > U2 ? (U1 > U3 ? U1 : U3) : (U2 > U3 ? U2 : U3);
-    static constexpr int SIZE0 = ((U + USZ + 1) / 2) * 2;
-    /* per-env stride residue mod 32 doubles (BIOIM_ENV_MOD >= 0, planar
-     * topologies; the spatial ones have no LDS to spare): it sets which banks
-     * the other env of a 32-lane group hits (ds_read_b64: 2 x 32 lanes;
-     * ds_read_b128: 16-lane groups mixing both envs) */
-    static constexpr int SIZE = (BIOIM_ENV_MOD >= 0 && T::PLANAR) ? SIZE0 + ((BIOIM_ENV_MOD - SIZE0 % 32) + 32) % 32 : SIZE0;
-};
-
-/* The realize cache (DState::cache): a step's realize runs at
- * the state the next step's first substep starts from, and a muscle model's
- * forces there do not depend on the excitations the policy sends next (they
- * enter only the activation rate).  So the realize also forms the implicit
- * system of that substep (h = the next step's substep length: M + h C + h^2 K
- * and its right-hand side, CJ / LIM at that h) and the muscles' fiber-velocity
- * roots, and stores them per env; the next launch's first substep loads them
- * and goes straight to the solve instead of a whole dynamics call.  Torque
- * models: the actuator torques are the controls, so their cached right-hand
- * side stops short of them and the cached substep adds this step's. */
-#ifndef BIOIM_REALIZE_CACHE
-#define BIOIM_REALIZE_CACHE 1
-#endif
-#ifndef BIOIM_REALIZE_CACHE_SPATIAL
-#define BIOIM_REALIZE_CACHE_SPATIAL 1
-#endif
-#ifndef BIOIM_REALIZE_CACHE_TORQUE
-#define BIOIM_REALIZE_CACHE_TORQUE 1
-#endif
-/* the spatial kernels load the cache row at the substep (0) or at kernel
- * start like the planar ones (1) */
-#ifndef BIOIM_CACHE_PREFETCH_SPATIAL
-#define BIOIM_CACHE_PREFETCH_SPATIAL 0
-#endif
-template <class T> struct CacheLay {
-    /* torque models: the cached right-hand side leaves out the actuator
-     * torques (the controls), which the cached substep adds */
-    static constexpr bool ON = BIOIM_REALIZE_CACHE &&
-                               (T::NM > 0 ? (T::PLANAR || BIOIM_REALIZE_CACHE_SPATIAL) : BIOIM_REALIZE_CACHE_TORQUE);
-    /* planar kernels load the row at kernel start, ahead of the action
-     * pre-processing; the spatial ones (no register headroom) at the substep */
-    static constexpr bool PREFETCH = T::PLANAR || BIOIM_CACHE_PREFETCH_SPATIAL;
-    static constexpr int ND = T::ND > 0 ? T::ND : 1, NP = ND * (ND + 1) / 2;
-    static constexpr int SYS = NP + ND;          /* [NP] packed lower M(h), [ND] rhs(h): LDS MP..RHS order */
-    static constexpr int MUS = SYS;              /* [NM][3] fiber-velocity root, dv/dl, clamped (0 / 1) */
-    static constexpr int H = MUS + 3 * T::NM;    /* the h the system was formed at */
-    static constexpr int DIM = ON ? H + 1 : 0;
-    static constexpr int PF = (SYS + T::G - 1) / T::G;   /* system values per lane */
-};
-
-/* apply_perturbations kernels only: per env 5 doubles after all env regions
- * (call time base, substep length, cursor segment [lo, hi), its force) */
-constexpr int PERT_SLOT = 5;
-
-DEV void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-/* the same fence inside a lane-divergent region: orders this wave's LDS
- * accesses (the active lanes' reads before their writes); lanes of one wave
- * execute in lockstep, so no lane can be behind */
-DEV void wave_sync_lanes() { wave_sync(); }
-
-/* Diagnostic build only (-DBIOIM_STAMPS, tools/stamps.py): per-phase shader
- * cycles of the first env of workgroup 0, accumulated over one launch. */
-#ifdef BIOIM_STAMPS
-#define STAMP(i)                                                                      \
-    do {                                                                              \
-        __builtin_amdgcn_sched_barrier(0);                                            \
-        unsigned long long t_ = __builtin_amdgcn_s_memtime();                         \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                                           \
-        if (blockIdx.x == 0 && threadIdx.x == 0) g_stamps[i] += t_ - stamp_prev;      \
-        stamp_prev = t_;                                                              \
-        __builtin_amdgcn_sched_barrier(0);                                            \
-    } while (0)
-#define STAMP_DECL unsigned long long stamp_prev = __builtin_amdgcn_s_memtime();
-#else
-#define STAMP(i) do {} while (0)
-#define STAMP_DECL
-#endif
-
-template <int I> DEV constexpr int tri(int k, int l) { return k * (k + 1) / 2 + l; }
-
 /* publish the coordinate values/speeds to LDS (QF/UF): dof lane d writes its
  * coordinate, lane 0 the locked coordinates (default value, zero speed) */
 template <class T, typename Real>
@@ -853,35 +364,6 @@ DEV void publish_coords(const DModel<Real> &M, const SModel<T, Real> &SM, Real *
  * giving the child-in-parent transform, the joint's relative velocity and
  * velocity-product acceleration in the parent frame, and the joint's
  * Plucker columns about the parent origin (accumulated per dof into SL). */
-/* BIOIM_FRONTEND (the step kernels' dynamics calls; the analysis kernels
- * reach these helpers through state_kinematics with FE = 0, the forms below
- * without it): waits and duplicate LDS traffic taken out of the kinematics
- * front end, every arithmetic operation and its order kept.  One bit per item:
- *   1 (FE_COLS)    kin_local sums a body's joint columns per local dof in
- *                  registers (0 + its axes' contributions, in axis order) and
- *                  stores each dof's words to SL once: no read-modify-write of
- *                  SL at a run-time dof index, no per-call zeroing of SL, and
- *                  an axis without a dof contributes to nothing (no sink row)
- *   2 (FE_KINDS)   planar kin_local: the linear / constant axis forms are
- *                  computed from unconditional loads and selected (as the
- *                  spline arm), no EXEC-masked arm per kind
- *   4 (FE_INERTIA) kin_chain hands its frame to body_inertia in registers, in
- *                  the same body-lane block: no reload of KB / AL, and the
- *                  columns run with the subtree sums' reads (one sync fewer)
- *   8 (FE_LEVEL0)  the chain's first level composes with the ground frame
- *                  (R = I, o = (-x0, 0, 0), no motion) by copy and offset
- * One byte per kernel family (TailSwitch): bits 0-7 the planar topologies'
- * kernels, 8-15 the spatial ones', 16-23 the fused two-topology kernels.
- * Shipped (same-box A/B): all four in the planar kernels.  None in
- * the spatial ones: FE_LEVEL0 changes result bits there (the fused kernels and
- * the parent build no longer agree with them bit for bit), FE_INERTIA alone
- * puts one spatial RK kernel on scratch, and FE_COLS | FE_INERTIA gained less
- * than the builds' round spread on Running3D.  None in the fused kernels, which
- * measured no faster with any of them. */
-#ifndef BIOIM_FRONTEND
-#define BIOIM_FRONTEND 0x00000F
-#endif
-constexpr int FE_COLS = 1, FE_KINDS = 2, FE_INERTIA = 4, FE_LEVEL0 = 8;
 
 /* a body's dofs as kin_local meets them: the local slot of (body, axis) is
  * the rank of the axis's dof among the body's distinct dofs in axis order */
@@ -1251,21 +733,6 @@ template <class T, typename Real> DEV void compose_ground(Frame<Real> &F, const 
 }
 
 /* identity joint (LOC slot NB) and the ground frame (KB/AL slot NB) */
-/* BIOIM_GROUND_ONCE (the step kernels): the ground slot's constants — the KB
- * rotation, its zero origin / velocity words and the zero AL row, which no
- * other code writes — go to LDS once per launch (kin_ground_const) and a call
- * writes only kb[9] = -x0.  The identity LOC slot lies in the union region:
- * where the call's force slots (TAU, CJ) end below it (ground_loc_free), only
- * the report's staging (OBS, REP) writes over it, and it is written once per
- * launch too and again before a realize that follows a report (the reset
- * realize); elsewhere (the spatial muscle topologies) it stays with the call.
- * Bits (TailSwitch): 1 the planar topologies' kernels, 2 the spatial ones',
- * 4 the fused two-topology kernels (env_kernel2, rollout_kernel2), which
- * measured no faster with it (C5 0.4687 -> 0.4708 ms same box) and keep the
- * per-call writes. */
-#ifndef BIOIM_GROUND_ONCE
-#define BIOIM_GROUND_ONCE 3
-#endif
 template <class T, typename Real> DEV constexpr bool ground_loc_free() {
     using LY = Lay<T, Real>;
     return LY::LOC + 24 * T::NB >= LY::TAU + LY::TAUN && LY::LOC + 24 * T::NB >= LY::CJ + LY::NS * LY::CJN;
@@ -1440,130 +907,7 @@ DEV void body_inertia(const SModel<T, Real> &SM, const DModel<Real> &M, Real *ld
     for (int i = 0; i < 3; ++i) { wb[i] = n[i] + t[i]; wb[3 + i] = f[i]; }
 }
 
-/* symmetric 3x3 (xx yy zz xy xz yz) times v, v's known zeros masked (ZB) */
-template <unsigned ZB, typename Real> DEV void symvm(const Real *J, const Real *v, Real *o) {
-    const int r0[3] = {0, 3, 4}, r1[3] = {3, 1, 5}, r2[3] = {4, 5, 2}, iv[3] = {0, 1, 2}, sg[3] = {1, 1, 1};
-    Real x = sum_m<0, ZB, 3>(J, v, r0, iv, sg), y = sum_m<0, ZB, 3>(J, v, r1, iv, sg), z = sum_m<0, ZB, 3>(J, v, r2, iv, sg);
-    o[0] = x; o[1] = y; o[2] = z;
-}
-/* symmetric 3x3 (xx yy zz xy xz yz) times v */
-template <typename Real> DEV void symv(const Real *J, const Real *v, Real *o) {
-    Real x = J[0] * v[0] + J[3] * v[1] + J[4] * v[2];
-    Real y = J[3] * v[0] + J[1] * v[1] + J[5] * v[2];
-    Real z = J[4] * v[0] + J[5] * v[1] + J[2] * v[2];
-    o[0] = x; o[1] = y; o[2] = z;
-}
-
-/* Tree-sparse LTL factorization M = L^T L and solve (Featherstone, Rigid
- * Body Dynamics Algorithms 6.3), unrolled at compile time over the
- * topology's dof tree: entry (k, i) of M is structurally non-zero only when
- * i is k or an ancestor dof of k, and factoring from the leaves up creates
- * no fill-in, so only those entries are touched (2D: 53 of the dense 121
- * multiply-adds, 3D: 257 of 457).  In place on the packed lower M; returns
- * false if not SPD. */
-template <class T> struct DofTree {
-    /* parent dof: the previous dof of the same body, else the last dof of
-     * the nearest ancestor body that has one, else -1 */
-    static constexpr int par(int d) {
-        for (int e = d - 1; e >= 0; --e)
-            if (T::dof_cb[e] == T::dof_cb[d]) return e;
-        for (int b = T::parent[T::dof_cb[d]]; b >= 0; b = T::parent[b]) {
-            int last = -1;
-            for (int e = 0; e < T::ND; ++e)
-                if (T::dof_cb[e] == b) last = e;
-            if (last >= 0) return last;
-        }
-        return -1;
-    }
-    /* i is a proper ancestor dof of k */
-    static constexpr bool anc(int k, int i) {
-        for (int j = par(k); j >= 0; j = par(j))
-            if (j == i) return true;
-        return false;
-    }
-    /* bit l set: l is k or an ancestor dof of k (the structurally non-zero
-     * entries (k, l) of row k of M) */
-    static constexpr unsigned path_mask(int k) {
-        unsigned m = 1u << k;
-        for (int j = par(k); j >= 0; j = par(j)) m |= 1u << j;
-        return m;
-    }
-    /* dof 0 is on every dof's root path (phase 3's row stores rely on it) */
-    static constexpr bool root_common() {
-        for (int k = 0; k < T::ND; ++k)
-            if (!(path_mask(k) & 1u)) return false;
-        return true;
-    }
-};
-
-template <class T, int N, typename Real> DEV bool ltl_solve(Real *A, Real *b) {
-    using DT = DofTree<T>;
-    bool ok = true;
-    Real inv[N];
-    /* factor: for k = N-1 .. 0 */
-    sfor<0, N>([&](auto kk) {
-        constexpr int k = N - 1 - decltype(kk)::value;
-        Real s = A[tri<0>(k, k)];
-        ok = ok && (s > 0);
-        const Real sp = s > 0 ? s : Real(1e-30);
-        const Real id = fast_rsqrt(sp), d = sp * id;
-        inv[k] = id;
-        A[tri<0>(k, k)] = d;
-        sfor<0, N>([&](auto iI) {
-            constexpr int i = decltype(iI)::value;
-            if constexpr (DT::anc(k, i)) A[tri<0>(k, i)] *= id;
-        });
-        sfor<0, N>([&](auto iI) {
-            constexpr int i = decltype(iI)::value;
-            if constexpr (DT::anc(k, i)) {
-                sfor<0, N>([&](auto jI) {
-                    constexpr int j = decltype(jI)::value;
-                    if constexpr (j == i || DT::anc(i, j)) A[tri<0>(i, j)] -= A[tri<0>(k, i)] * A[tri<0>(k, j)];
-                });
-            }
-        });
-    });
-    /* L^T y = b, leaves first */
-    sfor<0, N>([&](auto ii) {
-        constexpr int i = N - 1 - decltype(ii)::value;
-        b[i] *= inv[i];
-        sfor<0, N>([&](auto jI) {
-            constexpr int j = decltype(jI)::value;
-            if constexpr (DT::anc(i, j)) b[j] -= A[tri<0>(i, j)] * b[i];
-        });
-    });
-    /* L x = y, root first */
-    sfor<0, N>([&](auto iI) {
-        constexpr int i = decltype(iI)::value;
-        sfor<0, N>([&](auto jI) {
-            constexpr int j = decltype(jI)::value;
-            if constexpr (DT::anc(i, j)) b[i] -= A[tri<0>(i, j)] * b[j];
-        });
-        b[i] *= inv[i];
-    });
-    return ok;
-}
-
 /* ---------------------------------------------------- contact + limits */
-/* branch-free: the transition polynomial is evaluated everywhere and
- * selected (finite for any x) */
-template <bool BF, typename Real> DEV Real smooth_step(Real y0, Real y1, Real x0, Real x1, Real iw, Real x) {
-    if constexpr (!BF) {
-        if (x <= x0) return y0;
-        if (x >= x1) return y1;
-    }
-    Real t = (x - x0) * iw;   /* iw = 1 / (x1 - x0) */
-    const Real v = y0 + (y1 - y0) * t * t * t * (Real(10) + t * (Real(6) * t - Real(15)));
-    return x <= x0 ? y0 : (x >= x1 ? y1 : v);
-}
-template <bool BF, typename Real> DEV Real smooth_step_d(Real y0, Real y1, Real x0, Real x1, Real iw, Real x) {
-    if constexpr (!BF) {
-        if (x <= x0 || x >= x1) return 0;
-    }
-    Real t = (x - x0) * iw;
-    const Real v = (y1 - y0) * Real(30) * t * t * (Real(1) - t) * (Real(1) - t) * iw, zero = 0;
-    return ((x <= x0) | (x >= x1)) ? zero : v;
-}
 
 /* Hunt-Crossley sphere s (this lane) vs the ground plane.  Publishes the
  * sphere's wrench about the (shifted) ground origin (CW) and, for the
@@ -2557,17 +1901,6 @@ DEV void report_points(const SModel<T, Real> &SM, Real *lds, int lane, Real x0) 
     for (int i = 0; i < 3; ++i) { r[i] = pos[i]; r[3 + i] = vel[i]; }
 }
 
-/* REP slot of an OpenSim body index (-1 = COM) */
-template <class T> DEV constexpr int rep_slot(int ob) { return ob >= 0 ? ob : T::NOS; }
-
-/* observation offsets (get_state_dict order, muscle_walking_imitation_env2D.py:158-225) */
-template <class T> struct ObsLayout {
-    static constexpr int NTR = (T::TX >= 0) + (T::TY >= 0) + (T::TZ >= 0);
-    static constexpr int NQ = T::NC - NTR;
-    static constexpr int QPOS = 1, QVEL = QPOS + NQ, QACC = QVEL + T::NC, TGT = QACC + T::NC;
-    static constexpr int body(bool tgt) { return TGT + (tgt ? 2 * (T::NC - 1) : 0); }
-};
-
 DEV int clamp_row(int r, int nrows) { return r < 0 ? 0 : (r >= nrows ? nrows - 1 : r); }
 
 /* counter-based RNG (splitmix64) for device-drawn reset indices */
@@ -2963,14 +2296,6 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_e
  * write at run-time indices shared between lanes, sums in a fixed order: a
  * state's result does not depend on n or its neighbours.  Matrices, sets and
  * flags live in LDS; the per-lane arrays have compile-time indices only. */
-template <int G, typename V> DEV V group_min(V x) {
-#pragma unroll
-    for (int off = G / 2; off >= 1; off >>= 1) {
-        const V y = __shfl_xor(x, off, G);
-        x = y < x ? y : x;
-    }
-    return x;
-}
 
 template <typename P> struct SoFields {   /* bioim_static_opt (fp64 only) */
     int n, passive;
@@ -4554,7 +3879,6 @@ template <class T, typename Real> struct LaunchArgs {
  * Stage form, error norm, step control and the attempt cap follow
  * oracle/bioim_oracle.c integrate_rk_merson exactly; per state value the lane
  * keeps y0, K, E (three registers) besides the value itself. */
-#define BIOIM_RK_MAX_ATTEMPTS 4096
 template <typename Real> DEV void rk_update(int s, Real h, Real f, Real &y, Real &y0, Real &K, Real &E, Real &err) {
     switch (s) {
     case 0: y0 = y; K = f; E = Real(2) * f; y = y0 + h / Real(3) * f; break;

@@ -20,7 +20,7 @@ from bioimitation.osim import load_osim  # noqa: E402
 
 DATA = os.path.join(PKG_ROOT, 'bioimitation', 'data')
 # env flags baked into a kernel (MUSCLE, HAS_TZ, REWARD_FEET, DONE_CROSS, PD); the others
-# (RAW_ACTION, TARGET_OBS, GRF_OBS) are read at run time — csrc/bioim_step.hip: BIOIM_STRUCT_FLAGS
+# (RAW_ACTION, TARGET_OBS, GRF_OBS) are read at run time — csrc/bioim_config.h: BIOIM_STRUCT_FLAGS
 STRUCT_FLAGS = 0x8f
 
 
@@ -110,7 +110,7 @@ def is_planar(pk):
     move have no z component, gravity has none.  The kernels then carry the
     structural zeros of planar frames (R13 R23 R31 R32 = 0, R33 = 1; angular
     velocity/acceleration along z only; linear ones in the plane) as
-    constants (bioim_step.hip: Planar)."""
+    constants (bioim_math.h: Planar)."""
     def zrot(R):
         return R[2] == 0 and R[5] == 0 and R[6] == 0 and R[7] == 0 and R[8] == 1
     for c in range(pk.ncbody):

@@ -128,3 +128,32 @@ def test_build_id_covers_the_build_recipe():
     from bioimitation import _buildinfo
     assert any(p.endswith('__graft_entry__.py') for p in _buildinfo.SOURCES)
     assert _buildinfo.sources_present()
+
+
+def test_build_id_covers_every_included_source():
+    """csrc/bioim_step.hip is the one file handed to the compiler; its lowest
+    layers are headers it includes.  Every file its quoted #include lines reach
+    (transitively, through csrc/ and include/) is in _buildinfo.SOURCES, and
+    every csrc/*.h is reached: a header added later and not listed would
+    leave the build id as it was, and a stale library would load against
+    edited sources."""
+    from bioimitation import _buildinfo
+    dirs = (_buildinfo.CSRC, _buildinfo.INCLUDE)
+    start = os.path.join(_buildinfo.CSRC, 'bioim_step.hip')
+    reached, todo = set(), [start]
+    while todo:
+        path = todo.pop()
+        if path in reached:
+            continue
+        reached.add(path)
+        for name in re.findall(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', open(path).read(), flags=re.M):
+            found = [os.path.join(d, name) for d in (os.path.dirname(path),) + dirs if os.path.exists(os.path.join(d, name))]
+            assert found, f'{os.path.basename(path)} includes "{name}", which is in neither csrc/ nor include/'
+            todo.append(os.path.normpath(found[0]))
+    listed = {os.path.normpath(p) for p in _buildinfo.SOURCES}
+    unlisted = sorted(os.path.relpath(p, REPO) for p in reached - listed)
+    assert not unlisted, f'included by bioim_step.hip but not in _buildinfo.SOURCES: {unlisted}'
+    headers = {os.path.join(_buildinfo.CSRC, f) for f in os.listdir(_buildinfo.CSRC) if f.endswith('.h')}
+    orphans = sorted(os.path.relpath(p, REPO) for p in headers - reached)
+    assert not orphans, f'in csrc/ but not included from bioim_step.hip: {orphans}'
+    assert len(_buildinfo.SOURCES) == len(listed), 'a source is listed twice'

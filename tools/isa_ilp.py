@@ -8,11 +8,14 @@ latency, LDS latency, s_waitcnt) — calibrated on tools/ubench/lat2.hip
 FMA issue 5.8, 32-bit VALU 4.5, fp64 transcendental 16.5, ds_read latency
 ~53 cycles (dependent chain incl. the wait), SALU / s_nop 4).  The ratio
 model / issue-bound says how much of a block's time is dependency latency
-the schedule leaves exposed.
+the schedule leaves exposed.  With -gline-tables-only the last column names
+each block's three most frequent source lines as file:line (the assembler's
+.file table names the file: the kernel's lowest layers are headers).
 
     python tools/isa_ilp.py t1g.s <kernel-symbol-substring> [top]
 """
 import collections
+import os
 import re
 import sys
 
@@ -71,9 +74,14 @@ def split_ops(t):
 
 def blocks(path, sym):
     lines = open(path).read().split('\n')
+    files = {}   # .file index -> name (DWARF 5 gives directory and name, DWARF 4 the name alone)
+    for l in lines:
+        m = re.match(r'\s*\.file\s+(\d+)\s+"([^"]*)"(?:\s+"([^"]*)")?', l)
+        if m:
+            files[int(m.group(1))] = os.path.basename(m.group(3) or m.group(2))
     st = next(i for i, l in enumerate(lines) if l.startswith('_Z') and sym in l.split(':')[0] and ':' in l)
     en = next(i for i in range(st, len(lines)) if lines[i].startswith('.Lfunc_end'))
-    out, cur, loc, depth = [], None, 0, 0
+    out, cur, loc, depth = [], None, None, 0
     for l in lines[st:en]:
         if l.startswith('.LBB') or l.startswith('; %bb'):
             m = re.search(r'Depth=(\d+)', l)
@@ -86,7 +94,7 @@ def blocks(path, sym):
             continue
         if t.startswith('.loc'):
             f = t.split()
-            loc = int(f[2]) if f[1] == '0' else 0
+            loc = f'{files.get(int(f[1]), "?")}:{f[2]}'
             continue
         if t[0] == '.' or t.endswith(':'):
             continue
