@@ -15,7 +15,7 @@ from . import packdef as P
 PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get('BIOIM_LIB', os.path.join(PKG_ROOT, 'build', 'libbioim.so'))
 
-EXPORTS = ['bioim_create', 'bioim_destroy', 'bioim_reset', 'bioim_step', 'bioim_set_auto_reset', 'bioim_set_env_offset', 'bioim_set_io_strides', 'bioim_step_group', 'bioim_set_group_fusion', 'bioim_group_fused', 'bioim_set_reset_table', 'bioim_reset_table_rows', 'bioim_set_perturbation', 'bioim_id_eval', 'bioim_state_dim',
+EXPORTS = ['bioim_create', 'bioim_destroy', 'bioim_reset', 'bioim_step', 'bioim_set_auto_reset', 'bioim_set_env_offset', 'bioim_set_io_strides', 'bioim_step_group', 'bioim_set_group_fusion', 'bioim_group_fused', 'bioim_set_reset_table', 'bioim_reset_table_rows', 'bioim_set_perturbation', 'bioim_set_external_forces', 'bioim_id_eval', 'bioim_state_dim',
            'bioim_get_state', 'bioim_set_state', 'bioim_query', 'bioim_query_launch', 'bioim_stream', 'bioim_set_stream', 'bioim_sync',
            'bioim_last_error', 'bioim_modelpack_size', 'bioim_build_id', 'bioim_reset_count', 'bioim_set_final_obs', 'bioim_set_integrator', 'bioim_force_report_dim', 'bioim_set_force_report',
            'bioim_set_rk_budget', 'bioim_pending_count', 'bioim_set_active_mask', 'bioim_osim', 'bioim_osim_report_dim', 'bioim_eval_count', 'bioim_set_state_storage',
@@ -53,6 +53,7 @@ def load():
         'bioim_set_reset_table': (C.c_int, [C.c_void_p, C.c_int]),
         'bioim_reset_table_rows': (C.c_int, [C.c_void_p]),
         'bioim_set_perturbation': (C.c_int, [vp, C.c_int, C.c_int, dp, dp]),
+        'bioim_set_external_forces': (C.c_int, [vp, C.c_int, vp, vp, vp]),
         'bioim_id_eval': (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp]),
         'bioim_muscle_eval': (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         'bioim_static_opt': (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, vp, vp, vp, vp]),

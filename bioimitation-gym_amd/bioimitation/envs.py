@@ -180,6 +180,26 @@ class ImitationEnv:
         inf = [float(v) for v in out[nobs + 1:nobs + 1 + ninf]]
         return o, float(out[nobs]), inf, done
 
+    def set_external_forces(self, points, wrench=None, point_in='body'):
+        """External forces and torques on bodies (``VectorEnv.set_external_forces``
+        for this one env).  ``points``: body names, one per force slot;
+        ``wrench``: (K, 9) numbers, per slot ``fx fy fz px py pz tx ty tz``
+        (None: zeros).  Returns the (1, K, 9) device tensor every later step
+        reads; call again with new numbers, or write into the tensor.
+        ``points=None`` removes the forces."""
+        import torch
+        e = self._env
+        if points is None:
+            return e.set_external_forces(None)
+        if wrench is not None:
+            w = np.asarray(wrench, dtype=np.float64)
+            if w.ndim != 2 or w.shape[1] != 9:
+                raise ValueError(f'external forces: wrench must have shape (K, 9), got {w.shape}')
+            wrench = torch.as_tensor(w[None, :, :], dtype=e.dtype).contiguous().to(e.device)
+        out = e.set_external_forces(points, wrench, point_in)
+        self.osim_model._dirty()
+        return out
+
     # -- reference API -------------------------------------------------------
     def _out(self, obs, as_dict):
         o = obs[0] if isinstance(obs, np.ndarray) else obs[0].double().cpu().numpy()

@@ -146,6 +146,7 @@ class VectorEnv:
         self.info = torch.zeros((n, self.info_dim), dtype=self.dtype, device=self.device)
         self.final_obs = None
         self.perturbation = None
+        self.external_forces = None     # set_external_forces: (body names, frame names, the (N, K, 9) tensor)
         if (config or {}).get('apply_perturbations'):
             from .perturb import batch_points
             self.set_perturbation(*batch_points(env_id, n, seed=(config or {}).get('perturbation_seed', seed),
@@ -159,6 +160,9 @@ class VectorEnv:
         table by :func:`bioimitation.perturb.zoh_table`."""
         from .obslayout import load_names
         from .perturb import os_body_index, zoh_table
+        if x is not None and self.external_forces is not None:
+            raise ValueError('set_perturbation: external forces are set on this env (set_external_forces); a push '
+                             'is one force slot there')
         if x is None:
             _lib.check(self._L.bioim_set_perturbation(self._h, -1, 0, None, None))
             self.perturbation = None
@@ -170,6 +174,69 @@ class VectorEnv:
         xt = np.ascontiguousarray(xt)
         _lib.check(self._L.bioim_set_perturbation(self._h, ob, len(xt), xt.ctypes.data_as(dp), yt.ctypes.data_as(dp)))
         self.perturbation = (np.asarray(x, dtype=np.float64), yt)
+
+    def set_external_forces(self, points, wrench=None, point_in='body'):
+        """Per-env external forces and torques on bodies
+        (``bioimitation.external_forces``; ``bioim_set_external_forces``).
+        ``points``: up to 8 OpenSim body names, one per force slot (a body may
+        have several); ``point_in``: 'body' or 'ground', one for all or one
+        per slot — the frame the slot's point of application is given in.
+        ``wrench``: a contiguous (N, K, 9) tensor of the env's dtype on its
+        device, per env and slot ``fx fy fz px py pz tx ty tz`` (force and
+        torque in ground); None allocates zeros.  Returns the tensor every
+        later ``step``, ``reset``, ``osim`` call and rollout step reads at its
+        start: write into it between steps on the env's stream, like actions.
+        The values are held over a step; they are inputs, not state
+        (``state_rows`` / ``load_state`` / ``clone_envs`` leave them alone, an
+        auto-reset too) and are not sanitized.  ``points=None`` removes the
+        forces.  Not with ``apply_perturbations`` or ``integrator='rk-merson'``
+        (``ValueError``); a rollout then runs one launch per step."""
+        import torch
+        from . import external_forces as xf
+        if points is None:
+            self._bind_stream()
+            _lib.check(self._L.bioim_set_external_forces(self._h, 0, None, None, None))
+            self.external_forces = None
+            return None
+        if getattr(self, '_bk_bodies', None) is None:
+            from .obslayout import load_names
+            self._bk_bodies = list(load_names(self.env_id)['bodies'])
+        body, frame = xf.check_slots(self._bk_bodies, points, point_in)
+        xf.check_compatible(self.perturbation, self.integrator, getattr(self, 'rk_budget', 0))
+        k = int(body.size)
+        if wrench is None:
+            wrench = torch.zeros((self.num_envs, k, xf.ROW), dtype=self.dtype, device=self.device)
+        xf.check_wrench(wrench, self.num_envs, k, self.dtype, self.device)
+        ip = C.POINTER(C.c_int32)
+        self._bind_stream()
+        _lib.check(self._L.bioim_set_external_forces(self._h, k, body.ctypes.data_as(ip), frame.ctypes.data_as(ip),
+                                                     self._ptr(wrench)))
+        self.external_forces = (body, frame, wrench)
+        return wrench
+
+    def external_wrench_ground(self, env_ids=None, rows=None):
+        """The current external forces as the analyses take them (``ext`` of
+        ``joint_reaction`` / ``induced_accelerations``): ``[n][ncbody][6]``,
+        fx fy fz mx my mz on each composite body in the ground frame, the
+        moment about the ground origin; one row per env (or per listed env, in
+        the list's order).  Formed on the device from the envs' own
+        ``body_kinematics`` origins and rotations and the (N, K, 9) tensor as
+        it is now: no host round trip, no synchronization.  None when no
+        forces are set."""
+        import torch
+        from . import external_forces as xf
+        if self.external_forces is None:
+            return None
+        body, frame, wrench = self.external_forces
+        pk = self.pack
+        if env_ids is not None:
+            host, ids = self._id_list(env_ids, 'env', distinct=True)
+            if ids is None:
+                ids = self._upload_ids(host)
+            wrench = wrench.index_select(0, ids.long())
+        bk = self.body_kinematics(env_ids=env_ids, want=('origin', 'rot'), rows=rows)
+        cbody = [pk.osbody[b].cbody for b in range(pk.nosbody)]
+        return xf.wrench_ground(wrench, body, frame, cbody, pk.ncbody, bk['origin'][:, :, 0, :], bk['rot'])
 
     def set_reset_table(self, on: bool = True):
         """In-kernel auto-resets from the per-handle reset table (default on;
@@ -269,6 +336,9 @@ class VectorEnv:
         import torch
         if self.integrator != 'rk-merson' and attempts:
             raise ValueError("set_rk_budget needs config integrator='rk-merson'")
+        if attempts and self.external_forces is not None:
+            raise ValueError('set_rk_budget: external forces are set on this env (set_external_forces): '
+                             'semi-implicit only')
         self.rk_budget = int(attempts)
         if attempts and getattr(self, 'ready', None) is None:
             self.ready = torch.ones(self.num_envs, dtype=torch.uint8, device=self.device)
@@ -627,7 +697,8 @@ class VectorEnv:
             qdd, ft = rep['qdd'], rep['ft']
         if getattr(self, '_jr_table', None) is None:
             self._jr_table = jr.JointTable(self.env_id)
-        res = jr.Result(jr.launch(self, q, u, qdd, ft, None, True, frame, on, want))
+        ext = self.external_wrench_ground(env_ids, rows) if n and self.external_forces is not None else None
+        res = jr.Result(jr.launch(self, q, u, qdd, ft, ext, True, frame, on, want))
         res.table, res.frame, res.on = self._jr_table, frame, on
         return res
 
@@ -669,7 +740,8 @@ class VectorEnv:
                             m[a, pk.coordact[a].dof] = 1.0
                     self._ia_act_dof = torch.as_tensor(m).to(device=self.device, dtype=self.dtype, non_blocking=True)
                 tau_act = (rep['act'] @ self._ia_act_dof).contiguous()
-        res = ia.Result(ia.launch(self, q, u, ft, tau_act, None, kind, None, None, force_threshold, want))
+        ext = self.external_wrench_ground(env_ids, rows) if n and self.external_forces is not None else None
+        res = ia.Result(ia.launch(self, q, u, ft, tau_act, ext, kind, None, None, force_threshold, want))
         if getattr(self, '_ia_names', None) is None:
             from .obslayout import load_names
             names = load_names(self.env_id)
@@ -960,6 +1032,13 @@ class MixedVectorEnv:
         for e in self.envs:
             e.set_auto_reset(on)
         self._auto_reset = bool(on)
+
+    def set_external_forces(self, segment, points, wrench=None, point_in='body'):
+        """External body forces on one segment (``VectorEnv.set_external_forces``
+        of ``self.envs[segment]``: its own body names and (n_segment, K, 9)
+        tensor, which is returned).  With forces on either segment the group
+        steps and rolls out with one launch per segment."""
+        return self.envs[segment].set_external_forces(points, wrench, point_in)
 
     def set_active_mask(self, mask):
         """Per-env step mask over the whole batch: a (N,) uint8/bool device

@@ -97,6 +97,19 @@ template <class T> struct CacheLay {
  * (call time base, substep length, cursor segment [lo, hi), its force) */
 constexpr int PERT_SLOT = 5;
 
+/* external-force kernels only (bioim_set_external_forces): per env the
+ * caller's BIOIM_MAX_EXT rows of 9 values (force, point, torque), staged once
+ * per launch after all env regions.  LDS: the slots fit beside the image and
+ * the env regions; where they do not (the 7-body spatial muscle topology in
+ * fp64 has 832 bytes to spare, the slots take 9216) the body lanes read the
+ * caller's rows at each dynamics call instead. */
+constexpr int EXT_ROW = 9;
+template <class T, typename Real> struct ExtLay {
+    static constexpr int SLOT = BIOIM_MAX_EXT * EXT_ROW;   /* reals per env */
+    static constexpr size_t BYTES = (size_t)BIOIM_EPB * SLOT * sizeof(Real);
+    static constexpr bool LDS = smodel_bytes<T, Real>() + (size_t)BIOIM_EPB * Lay<T, Real>::SIZE * sizeof(Real) + BYTES <= 163840;
+};
+
 /* REP slot of an OpenSim body index (-1 = COM) */
 template <class T> DEV constexpr int rep_slot(int ob) { return ob >= 0 ? ob : T::NOS; }
 

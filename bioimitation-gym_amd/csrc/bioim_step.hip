@@ -1346,6 +1346,56 @@ template <typename Real> struct PertArgs {
     int n, ob, env, N;
 };
 
+/* bioim_set_external_forces as the EXT kernels take it (a launch argument of
+ * its own, so LaunchArgs and with it every other kernel stay as they are):
+ * rows — the caller's [N][k][9]; inside env_block, one env's k rows (its
+ * staged LDS slot, or its rows of the caller's buffer where ExtLay::LDS is
+ * false).  body: slot j's OpenSim body in bits [8j, 8j + 8); ground: bit j set
+ * for a ground-frame point.  Wave-uniform, read with shifts (no indexed
+ * argument array). */
+template <typename Real> struct ExtArgs {
+    const Real *rows;
+    int k;
+    uint32_t ground;
+    uint64_t body;
+};
+
+/* The env's external wrenches on composite body `lane` (its own lane, after
+ * body_inertia stored WB): per slot of an OpenSim body of this composite body,
+ * in slot order, the force, its moment about the kernel's frame origin (the
+ * floating origin x0 on the ground x axis) and the torque, subtracted from
+ * the body's Newton-Euler wrench like the push.  A body-frame point goes
+ * through the OpenSim body's frame in the composite body (os_p, os_R), a
+ * ground-frame point is shifted by x0. */
+template <class T, typename Real>
+DEV void ext_apply(const DModel<Real> &M, const SModel<T, Real> &SM, const ExtArgs<Real> &X, Real *lds, int lane, Real x0) {
+    using LY = Lay<T, Real>;
+    const Real *kb = lds + LY::KB + 18 * lane;
+    Real *wb = lds + LY::WB + 6 * lane;
+#pragma unroll 1
+    for (int j = 0; j < X.k; ++j) {
+        const int ob = (int)((X.body >> (8 * j)) & 0xFFu);
+        if (lane != SM.os_cb[ob]) continue;
+        const Real *row = X.rows + EXT_ROW * j;
+        const Real f[3] = {row[0], row[1], row[2]}, pt[3] = {row[3], row[4], row[5]};
+        Real r[3], m[3];
+        if ((X.ground >> j) & 1u) {
+            r[0] = pt[0] - x0; r[1] = pt[1]; r[2] = pt[2];
+        } else {
+            Real pl[3], pc[3];
+            mv3(M.os_R[ob], pt, pl);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) pc[i] = SM.os_p[ob][i] + pl[i];
+            mv3(kb, pc, r);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) r[i] += kb[9 + i];
+        }
+        cross3(r, f, m);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { wb[i] -= m[i] + row[6 + i]; wb[3 + i] -= f[i]; }
+    }
+}
+
 /* Force of the env's zero-order-hold table at the call time t0 + k*dt (the
  * slot's base and step, written by lane 0 before the call); the segment
  * cursor [lo, hi) and its value live in the slot, so a binary search over
@@ -1425,14 +1475,15 @@ template <class T, bool FUSED = false> struct TailSwitch {
     /* the family's BIOIM_FRONTEND byte (FE_* bits) */
     static constexpr int FE = (BIOIM_FRONTEND >> (FUSED ? 16 : (T::PLANAR ? 0 : 8))) & 0xFF;
 };
-template <class T, typename Real, bool PERT, bool BF_ROWS, bool IMP, bool CACHE = false, class TS = TailSwitch<T>>
+template <class T, typename Real, bool PERT, bool BF_ROWS, bool IMP, bool CACHE = false, class TS = TailSwitch<T>, bool EXT = false>
 DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Real ud,
                   const Real (&act)[Lay<T, Real>::MPL], const Real (&lce)[Lay<T, Real>::MPL],
                   const Real (&control)[Lay<T, Real>::MPL], int lane, Real *lds, Real h, bool equilibrate,
-                  const PertArgs<Real> &P, double *pslot, int pk, Dyn<T, Real> &D, const CacheIO<T, Real> &CI) {
+                  const PertArgs<Real> &P, double *pslot, int pk, Dyn<T, Real> &D, const CacheIO<T, Real> &CI,
+                  const ExtArgs<Real> &X = ExtArgs<Real>{}) {
     using LY = Lay<T, Real>;
     constexpr int ND = LY::ND, NP = LY::NP, NB = T::NB, G = T::G, MPL = LY::MPL;
-    static_assert(!CACHE || (CacheLay<T>::ON && IMP && !PERT), "the realize cache: the default (semi-implicit, no push) step kernels");
+    static_assert(!CACHE || (CacheLay<T>::ON && IMP && !PERT && !EXT), "the realize cache: the default (semi-implicit, no push, no external forces) step kernels");
     static_assert(NB < G && ND <= G, "lane NB writes the ground slot; one lane per dof");
     /* the semi-implicit planar kernels: the implicit contact / limit terms
      * without a branch on h (the spatial kernels keep it: register budget) */
@@ -1536,6 +1587,8 @@ DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Rea
             wb[2] += (p[1] + kb[10]) * fpx;
             wb[3] -= fpx;
         }
+        /* bioim_set_external_forces: the env's held wrenches, same place */
+        if constexpr (EXT) ext_apply<T, Real>(M, SM, X, lds, lane, x0);
     };
     if constexpr ((FE & FE_INERTIA) != 0) {
         /* the body lane goes from its chain to its inertia and wrench with the
@@ -4302,8 +4355,9 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_e
 /* One 256-thread workgroup = 256/G envs of segment `a`, block `blk`.
  * RK: the reference integrator (adaptive Kutta-Merson) instead of the
  * fixed semi-implicit substeps. */
-template <class T, typename Real, bool PERT, bool RK, bool REP, bool FUSED = false>
-DEV void env_block(const LaunchArgs<T, Real> &a, int blk) {
+template <class T, typename Real, bool PERT, bool RK, bool REP, bool FUSED = false, bool EXT = false>
+DEV void env_block(const LaunchArgs<T, Real> &a, int blk, const ExtArgs<Real> &xa = ExtArgs<Real>{}) {
+    static_assert(!EXT || (!PERT && !RK && !FUSED), "external forces: the semi-implicit step and report kernels only");
     using LY = Lay<T, Real>;
     using TS = TailSwitch<T, FUSED>;
     constexpr int G = T::G, ND = LY::ND, NA = T::NA, NM = T::NM;
@@ -4400,7 +4454,7 @@ DEV void env_block(const LaunchArgs<T, Real> &a, int blk) {
      * from the last launch's realize when that row is valid for this state
      * and was formed at this step's substep length (checked below); loaded
      * here, ahead of the action pre-processing */
-    constexpr bool CACHE = CacheLay<T>::ON && !PERT && !RK && !REP;
+    constexpr bool CACHE = CacheLay<T>::ON && !PERT && !RK && !REP && !EXT;
     CacheIO<T, Real> CI;
     bool cache_valid = false;
     Real cache_h = 0;
@@ -4454,6 +4508,22 @@ DEV void env_block(const LaunchArgs<T, Real> &a, int blk) {
     const PertArgs<Real> PA{a.pert_x, a.pert_y, a.pert_n, a.pert_ob, env, N};
     double *pslot = reinterpret_cast<double *>(smem_raw + SMB + sizeof(Real) * EPB * LY::SIZE) + PERT_SLOT * slot;
     if (PERT && lane == 0) { pslot[0] = t; pslot[1] = 0; pslot[2] = 0; pslot[3] = -1; pslot[4] = 0; }
+    /* bioim_set_external_forces: this env's rows, read once per launch into
+     * its slot after the env regions (ExtLay; the env's own lanes write and
+     * read it, and the first dynamics call syncs before the body lanes do);
+     * held over every substep, the realize and an auto-reset's realize */
+    ExtArgs<Real> XE = xa;
+    if constexpr (EXT) {
+        const int nx = xa.k * EXT_ROW;
+        const Real *xrow = xa.rows + GIDX((size_t)env * nx, (size_t)N * nx);
+        if constexpr (ExtLay<T, Real>::LDS) {
+            Real *xs = reinterpret_cast<Real *>(smem_raw + SMB + sizeof(Real) * EPB * LY::SIZE) + ExtLay<T, Real>::SLOT * slot;
+            for (int i = lane; i < nx; i += G) xs[i] = GAT(xrow, i, nx);
+            XE.rows = xs;
+        } else {
+            XE.rows = xrow;
+        }
+    }
     /* OsimModel.integrate (opensim_wrapper.py:299-301): istep += 1, then
      * integrate to the absolute time step_size * istep with the held controls */
     auto begin_integrate = [&]() {
@@ -4705,9 +4775,9 @@ DEV void env_block(const LaunchArgs<T, Real> &a, int blk) {
             /* RK: explicit accelerations (h = 0, the implicit terms compile away) */
             /* branch-free phase-3 row stores, except in the spatial RK kernels
              * (they would take those kernels past the 512-register budget) */
-            dynamics<T, Real, PERT, !RK || T::PLANAR, !RK, CACHE, TS>(*(const DModel<Real> *)Mi, SM, qd, ud, act, lce, control, lane, lds,
+            dynamics<T, Real, PERT, !RK || T::PLANAR, !RK, CACHE, TS, EXT>(*(const DModel<Real> *)Mi, SM, qd, ud, act, lce, control, lane, lds,
                                     RK ? Real(0) : (sub ? dt : Real(0)), eq && NM > 0, PA, pslot,
-                                    RK ? 0 : M.nsub - remaining, D, CI);
+                                    RK ? 0 : M.nsub - remaining, D, CI, XE);
         }
         if (RK && sub) {
             const Real h = Real(rk_h);
@@ -5079,7 +5149,7 @@ DEV void env_block(const LaunchArgs<T, Real> &a, int blk) {
             pending_reset = true;
             do_reset = true;
             reset_row = draw_index(a.seed, a.env_offset + env, resets, M.reset_hi);
-            if constexpr ((!RK || (BIOIM_RESET_TAB_RK && (T::PLANAR || BIOIM_RESET_TAB_RK_SPATIAL))) && !PERT && !REP) {
+            if constexpr ((!RK || (BIOIM_RESET_TAB_RK && (T::PLANAR || BIOIM_RESET_TAB_RK_SPATIAL))) && !PERT && !REP && !EXT) {
                 /* the reset table (LaunchArgs::reset_tab): the state the reset
                  * realize would leave (reference row, default activation,
                  * equilibrium fiber lengths) and its observation, without a
@@ -5247,6 +5317,15 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_e
     const unsigned w = blockIdx.x * (BIOIM_EPB * T::G / 64) + threadIdx.x / 64;
     if ((threadIdx.x & 63) == 0 && w < BIOIM_WAVETIME_N) g_wavetime[w] = __builtin_amdgcn_s_memtime() - w0;
 #endif
+}
+
+/* EXT: the external-force kernels (bioim_set_external_forces) — the
+ * semi-implicit step (modes 0 and 1) and its REP variant with the env's held
+ * wrenches added in the dynamics call; separate instantiations under a name
+ * of their own, so every other kernel is untouched by them */
+template <class T, typename Real, bool REP>
+__global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_eu(1, 1))) void env_kernel_ext(LaunchArgs<T, Real> a, ExtArgs<Real> x) {
+    env_block<T, Real, false, false, REP, false, true>(a, blockIdx.x, x);
 }
 
 
@@ -5981,6 +6060,13 @@ struct bioim_handle {
     void *dstate;       /* DState<Real> (host copy of pointers) */
     void *pert_x, *pert_y; /* apply_perturbations table: double [pert_n], Real [pert_n][n] */
     int pert_n, pert_ob;
+    /* bioim_set_external_forces: the caller's device rows [n][ext_k][9], slot
+     * j's OpenSim body in bits [8j, 8j + 8) of ext_body, bit j of ext_ground
+     * set for a ground-frame point; ext_k == 0: off */
+    const void *ext_wrench;
+    int ext_k;
+    uint32_t ext_ground;
+    uint64_t ext_body;
     void *final_obs;    /* caller's device buffer [n][obs_stride] or null (bioim_set_final_obs) */
     void *force_out;    /* caller's device buffer [n][force_dim] or null (bioim_set_force_report) */
     void *traj;         /* caller's device buffers (bioim_set_state_storage) or null */
@@ -6008,7 +6094,7 @@ struct bioim_handle {
  * default kernels (no push table, semi-implicit) and no force report or
  * state storage (their rows come from the reset realize itself) */
 static inline bool reset_table_wanted(const bioim_handle_t *h) {
-    return h->reset_tab_on && h->auto_reset && h->pert_n == 0 && (!h->rk || (BIOIM_RESET_TAB_RK && (h->planar || BIOIM_RESET_TAB_RK_SPATIAL))) &&
+    return h->reset_tab_on && h->auto_reset && h->pert_n == 0 && h->ext_k == 0 && (!h->rk || (BIOIM_RESET_TAB_RK && (h->planar || BIOIM_RESET_TAB_RK_SPATIAL))) &&
            !h->force_out && !h->traj;
 }
 static inline bool reset_table_eligible(const bioim_handle_t *h) { return h->reset_tab && reset_table_wanted(h); }
@@ -6026,6 +6112,11 @@ namespace {
 template <class T, typename Real, bool PERT = false> constexpr size_t lds_bytes() {
     return smodel_bytes<T, Real>() + (size_t)BIOIM_EPB * Lay<T, Real>::SIZE * sizeof(Real) +
            (PERT ? (size_t)BIOIM_EPB * PERT_SLOT * sizeof(double) : 0);
+}
+
+/* the EXT kernels: the env regions, then the staged rows where they fit (ExtLay) */
+template <class T, typename Real> constexpr size_t lds_bytes_ext() {
+    return lds_bytes<T, Real, false>() + (ExtLay<T, Real>::LDS ? ExtLay<T, Real>::BYTES : 0);
 }
 
 /* bioim_osim_report_dim (include/bioim.h layout) */
@@ -6094,7 +6185,7 @@ void launch_impl(bioim_handle_t *h, int mode, const void *actions, void *obs, vo
      * with controls it writes ctl, which the stored system excludes and the
      * next step's actuate replaces): the rows stay valid across it, so a
      * read-only query leaves the next step's bits alone */
-    const bool default_kernel = mode != 2 && a.pert_n == 0 && !h->rk;
+    const bool default_kernel = mode != 2 && a.pert_n == 0 && !h->rk && h->ext_k == 0;
     const bool reads_only = mode == 2 && oc && oc->op == BIOIM_OSIM_REALIZE;
     if constexpr (CacheLay<T>::ON) {
         if (!default_kernel && !reads_only && h->cache_live) {
@@ -6102,6 +6193,15 @@ void launch_impl(bioim_handle_t *h, int mode, const void *actions, void *obs, vo
             h->cache_live = 0;
         }
         if (default_kernel) h->cache_live = 1;
+    }
+    if (h->ext_k > 0) {   /* external forces (no push table, semi-implicit: bioim_set_external_forces) */
+        ExtArgs<Real> x;
+        x.rows = reinterpret_cast<const Real *>(h->ext_wrench);
+        x.k = h->ext_k; x.ground = h->ext_ground; x.body = h->ext_body;
+        constexpr size_t ldsx = lds_bytes_ext<T, Real>();
+        if (mode == 2) hipLaunchKernelGGL((env_kernel_ext<T, Real, true>), g, b, ldsx, h->stream, a, x);
+        else hipLaunchKernelGGL((env_kernel_ext<T, Real, false>), g, b, ldsx, h->stream, a, x);
+        return;
     }
     if (mode == 2) {   /* OsimModel calls: the REP kernels */
         if (a.pert_n > 0 && h->rk) hipLaunchKernelGGL((env_kernel<T, Real, true, true, true>), g, b, lds1, h->stream, a);
@@ -6305,6 +6405,9 @@ template <class T, typename Real> int upload_smodel(bioim_handle_t *h) {
     ALLOW_LDS((env_kernel<T, Real, true, false, true>), (lds_bytes<T, Real, true>()));
     ALLOW_LDS((env_kernel<T, Real, false, true, true>), (lds_bytes<T, Real, false>()));
     ALLOW_LDS((env_kernel<T, Real, true, true, true>), (lds_bytes<T, Real, true>()));
+    static_assert(lds_bytes_ext<T, Real>() <= 163840, "LDS image + env regions + external-force slots exceed 160 KiB");
+    ALLOW_LDS((env_kernel_ext<T, Real, false>), (lds_bytes_ext<T, Real>()));
+    ALLOW_LDS((env_kernel_ext<T, Real, true>), (lds_bytes_ext<T, Real>()));
     ALLOW_LDS((id_kernel<T, Real>), (lds_bytes<T, Real, false>()));
     ALLOW_LDS((rollout_kernel<T, Real>), (lds_bytes<T, Real, false>()));
     if constexpr (T::NM > 0) ALLOW_LDS((ma_kernel<T, Real>), (lds_bytes<T, Real, false>()));
@@ -6650,6 +6753,7 @@ int bioim_create(const bioim_modelpack_t *pack, int n_envs, int device, int prec
     h->obs_dim = pack->obs_dim; h->info_dim = pack->info_dim; h->nsub = pack->nsub; h->auto_reset = 0;
     h->env_offset = 0;
     h->pert_n = 0; h->pert_ob = -1;
+    h->ext_wrench = nullptr; h->ext_k = 0; h->ext_ground = 0; h->ext_body = 0;
     h->reset_tab = nullptr; h->reset_tab_on = 1; h->cache_live = 0;
     h->jr_model = nullptr; h->jr_smodel = nullptr; h->rk_budgeted = 0;
     h->rollout_live = nullptr; h->last_rollout_fused = 0; h->last_rollout_group_fused = 0;
@@ -6834,6 +6938,8 @@ int bioim_set_auto_reset(bioim_handle_t *h, int on) {
 int bioim_set_integrator(bioim_handle_t *h, int kind, double accuracy) {
     if (!h || kind < 0 || kind > 1 || (kind == 1 && !(accuracy > 0)))
         return fail(BIOIM_E_ARG, "bioim_set_integrator: kind 0 (semi-implicit) or 1 (RK-Merson, accuracy > 0)");
+    if (kind == 1 && h->ext_k > 0)
+        return fail(BIOIM_E_ARG, "bioim_set_integrator: external forces are set (bioim_set_external_forces): semi-implicit only");
     if (kind != h->rk) {
         const int np = bioim_pending_count(h);
         if (np < 0) return np;
@@ -6846,6 +6952,8 @@ int bioim_set_integrator(bioim_handle_t *h, int kind, double accuracy) {
 
 int bioim_set_rk_budget(bioim_handle_t *h, int attempts, uint8_t *ready_out) {
     if (!h || attempts < 0) return fail(BIOIM_E_ARG, "bioim_set_rk_budget: null handle or negative budget");
+    if (attempts > 0 && h->ext_k > 0)
+        return fail(BIOIM_E_ARG, "bioim_set_rk_budget: external forces are set (bioim_set_external_forces): semi-implicit only");
     h->rk_budget = attempts;
     if (attempts > 0) h->rk_budgeted = 1;
     h->ready_out = ready_out;
@@ -6934,7 +7042,8 @@ static int group_step_enqueue(bioim_handle_t **hs, int nh, const void *actions, 
      * and that run the default step kernels (no push table, semi-implicit):
      * one launch, workgroups [0, B0) segment 0, the rest segment 1 */
     *fused = 0;
-    if (nh == 2 && g_group_fusion && hs[0]->pert_n == 0 && hs[1]->pert_n == 0 && !hs[0]->rk && !hs[1]->rk) {
+    if (nh == 2 && g_group_fusion && hs[0]->pert_n == 0 && hs[1]->pert_n == 0 && !hs[0]->rk && !hs[1]->rk &&
+        hs[0]->ext_k == 0 && hs[1]->ext_k == 0) {
         const int rc = bioim_fused_launch(hs[0], hs[1], actions, obs, reward, done, info);
         if (rc < 0) return rc;
         if (rc == 1) {
@@ -6993,6 +7102,9 @@ int bioim_step_group(bioim_handle_t **hs, int nh, const void *actions, void *obs
 int bioim_set_perturbation(bioim_handle_t *h, int os_body, int npts, const double *x, const double *y) {
     if (!h || npts < 0 || (npts > 0 && (!x || !y || os_body < 0 || os_body >= h->pack.nosbody)))
         return fail(BIOIM_E_ARG, "bioim_set_perturbation: bad arguments");
+    if (npts > 0 && h->ext_k > 0)
+        return fail(BIOIM_E_ARG, "bioim_set_perturbation: external forces are set (bioim_set_external_forces); "
+                                 "a push is one force slot there");
     for (int k = 0; k + 1 < npts; ++k)
         if (!(x[k] < x[k + 1])) return fail(BIOIM_E_ARG, "bioim_set_perturbation: breakpoints must increase");
     HIPCHK(hipSetDevice(h->device));
@@ -7017,6 +7129,45 @@ int bioim_set_perturbation(bioim_handle_t *h, int os_body, int npts, const doubl
     HIPCHK(hipMemcpy(h->pert_y, yt.data(), yt.size(), hipMemcpyHostToDevice));
     h->pert_n = npts;
     h->pert_ob = os_body;
+    return 0;
+}
+
+int bioim_set_external_forces(bioim_handle_t *h, int k, const int32_t *os_body, const int32_t *point_frame,
+                              const void *wrench) {
+    if (!h) return fail(BIOIM_E_ARG, "bioim_set_external_forces: null handle");
+    if (k < 0 || k > BIOIM_MAX_EXT) return fail(BIOIM_E_ARG, "bioim_set_external_forces: k must be in [0, BIOIM_MAX_EXT]");
+    if (k > 0 && (!os_body || !point_frame || !wrench))
+        return fail(BIOIM_E_ARG, "bioim_set_external_forces: null os_body, point_frame or wrench");
+    for (int j = 0; j < k; ++j)
+        if (os_body[j] < 0 || os_body[j] >= h->pack.nosbody)
+            return fail(BIOIM_E_ARG, "bioim_set_external_forces: slot " + std::to_string(j) + ": no OpenSim body " +
+                                         std::to_string(os_body[j]));
+    for (int j = 0; j < k; ++j)
+        if (point_frame[j] != BIOIM_EXT_POINT_BODY && point_frame[j] != BIOIM_EXT_POINT_GROUND)
+            return fail(BIOIM_E_ARG, "bioim_set_external_forces: slot " + std::to_string(j) +
+                                         ": point_frame must be BIOIM_EXT_POINT_BODY or BIOIM_EXT_POINT_GROUND");
+    if (k > 0 && h->pert_n > 0)
+        return fail(BIOIM_E_ARG, "bioim_set_external_forces: a perturbation table is set (bioim_set_perturbation); "
+                                 "a push is one force slot here");
+    if (k > 0 && (h->rk || h->rk_budget > 0))
+        return fail(BIOIM_E_ARG, "bioim_set_external_forces: the semi-implicit integrator only (RK-Merson or an RK budget is set)");
+    /* the default step kernels' realize cache holds systems formed without
+     * these forces or, once they are gone, must not outlive them: the flags
+     * are cleared on the handle's stream when the forces are removed (a
+     * launch with forces set clears them itself, launch_impl) */
+    if (k == 0 && h->ext_k > 0 && cache_dim(h) > 0) {
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipMemsetAsync(plane_base(h, *find_plane("cache_ok")), 0, sizeof(int32_t) * (size_t)h->n, h->stream));
+        h->cache_live = 0;
+    }
+    uint64_t body = 0;
+    uint32_t ground = 0;
+    for (int j = 0; j < k; ++j) {
+        body |= (uint64_t)(uint32_t)os_body[j] << (8 * j);
+        if (point_frame[j] == BIOIM_EXT_POINT_GROUND) ground |= 1u << j;
+    }
+    h->ext_k = k; h->ext_body = body; h->ext_ground = ground;
+    h->ext_wrench = k > 0 ? wrench : nullptr;
     return 0;
 }
 
@@ -7606,7 +7757,7 @@ template <typename Real> static void rollout_host_loop(bioim_handle_t *h, const 
 /* the configurations rollout_kernel covers: the default step kernel's
  * (semi-implicit, no push table) without a force report or state storage */
 static inline bool rollout_fusable(const bioim_handle_t *h) {
-    return h->ops.rollout && !h->rk && h->pert_n == 0 && !h->force_out && !h->traj;
+    return h->ops.rollout && !h->rk && h->pert_n == 0 && h->ext_k == 0 && !h->force_out && !h->traj;
 }
 
 int bioim_rollout(bioim_handle_t *h, const void *actions, int steps, int64_t action_step_stride, void *obs_seq,

@@ -135,6 +135,39 @@ int bioim_group_fused(const bioim_handle_t *h);
  * double[npts], strictly increasing, shared by all envs; y: host double
  * [N][npts].  npts = 0 removes the force.  Synchronous (copies to device). */
 int bioim_set_perturbation(bioim_handle_t *h, int os_body, int npts, const double *x, const double *y);
+/* Per-env external body forces (OpenSim's PrescribedForce / ExternalForce;
+ * no counterpart in the reference envs beyond the torso push above): up to
+ * BIOIM_MAX_EXT force slots per handle.  Slot j acts on OpenSim body
+ * os_body[j] (ModelPack osbody index) and takes its point of application in
+ * that body's frame (BIOIM_EXT_POINT_BODY: the point moves with the body and
+ * is evaluated at every dynamics call) or in the ground frame
+ * (BIOIM_EXT_POINT_GROUND: fixed in space); both are the same for all envs.
+ * wrench: the caller's device buffer [N][k][9] in the handle's precision,
+ * per env and slot (fx fy fz, px py pz, tx ty tz) — ExternalForce's column
+ * order: force in ground, point, torque in ground.  The buffer is read, never
+ * written, by every later step, reset, OsimModel call and every step of a
+ * rollout, once per env at the start of the launch; within a step the values
+ * are held over all substeps and the realize.  The caller writes new values
+ * between steps on the handle's stream, like actions.  The wrench is an input,
+ * not state: bioim_copy_state_rows / bioim_load_state / bioim_clone_envs do
+ * not carry it, an auto-reset leaves it, and it is not sanitized (a
+ * non-finite entry makes that env's state non-finite and the step's finite
+ * check sets its done flag; other envs are untouched).  Two slots on one body
+ * add in slot order.  While forces are set the step runs kernels of its own
+ * (semi-implicit integrator, in-launch auto-reset, no realize cache), a
+ * rollout runs as one launch per step and a group step as one launch per
+ * segment.  k = 0 removes the forces (the arrays are ignored).
+ * Errors (BIOIM_E_ARG), checked in this order before anything else happens:
+ * null handle; k outside [0, BIOIM_MAX_EXT]; a null array with k > 0; a body
+ * outside [0, nosbody); a frame that is neither constant; a perturbation
+ * table set (bioim_set_perturbation: a push is one slot here); RK-Merson or
+ * an RK budget set.  With forces set, bioim_set_perturbation (npts > 0),
+ * bioim_set_integrator (kind 1) and bioim_set_rk_budget (attempts > 0) are
+ * refused the same way.  No device allocation, no synchronization. */
+#define BIOIM_MAX_EXT 8
+enum { BIOIM_EXT_POINT_BODY = 0, BIOIM_EXT_POINT_GROUND = 1 };
+int bioim_set_external_forces(bioim_handle_t *h, int k, const int32_t *os_body /* host [k] */,
+                              const int32_t *point_frame /* host [k] */, const void *wrench /* device [N][k][9] */);
 /* Inverse-dynamics primitives of the reference's InverseDynamics helper
  * (bioimitation/imitation_envs/inverse_dynamics/inverse_dynamics.cpp:45-205;
  * Boost.Python, built against OpenSim) on the handle's model, batched over n
