@@ -24,7 +24,8 @@ INCLUDE = os.path.join(REPO, 'include')
 # and checks this list against them).
 SOURCES = [os.path.join(CSRC, f) for f in (
     'bioim_step.hip', 'bioim_device.h', 'topologies.h',
-    'bioim_config.h', 'bioim_math.h', 'bioim_diag.h', 'bioim_layout.h')] + \
+    'bioim_config.h', 'bioim_math.h', 'bioim_diag.h', 'bioim_layout.h',
+    'bioim_curves.h', 'bioim_kinematics.h')] + \
     [os.path.join(INCLUDE, f) for f in ('bioim.h', 'bioim_modelpack.h')] + \
     [os.path.join(REPO, '__graft_entry__.py')]   # the per-object -D unit selectors and the link line live there
 

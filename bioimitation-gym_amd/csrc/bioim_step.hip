@@ -46,866 +46,8 @@
 #include "bioim_math.h"
 #include "bioim_diag.h"
 #include "bioim_layout.h"
-
-/* ------------------------------------------------------------ functions */
-template <class T, typename Real>
-DEV void spline_eval(const SModel<T, Real> &SM, int off, int n, Real q, Real &f, Real &f1, Real &f2) {
-    Real x0 = SM.kx[off], xn = SM.kx[off + n - 1];
-    if (q < x0) { f = SM.ky[off] + (q - x0) * SM.kb[off]; f1 = SM.kb[off]; f2 = 0; return; }
-    if (q > xn) {
-        int j = off + n - 1;
-        f = SM.ky[j] + (q - xn) * SM.kb[j]; f1 = SM.kb[j]; f2 = 0; return;
-    }
-    /* interval search: fixed trip count, all loads independent (one LDS wait) */
-    int k = 0;
-#pragma unroll
-    for (int i = 1; i < T::NKMAX - 1; ++i) {
-        Real xi = SM.kx[off + (i < n - 1 ? i : 0)];
-        k += (i < n - 1 && q > xi) ? 1 : 0;
-    }
-    int j = off + k;
-    Real dx = q - SM.kx[j], b = SM.kb[j], c = SM.kc[j], d = SM.kd[j];
-    f = SM.ky[j] + dx * (b + dx * (c + dx * d));
-    f1 = b + dx * (Real(2) * c + Real(3) * dx * d);
-    f2 = Real(2) * c + Real(6) * dx * d;
-}
-
-/* value and first two derivatives of function fi (fi < 0: absent axis, 0) */
-template <class T, typename Real>
-DEV void fn_eval(const SModel<T, Real> &SM, int fi, Real q, Real &f, Real &f1, Real &f2) {
-    f = 0; f1 = 0; f2 = 0;
-    if (fi < 0) return;
-    const SFn<Real> &F = SM.fn[fi];
-    if (F.type == BIOIM_FN_CONST) { f = F.b; }
-    else if (F.type == BIOIM_FN_LINEAR) { f = F.a * q + F.b; f1 = F.a; }
-    else {
-        Real s, s1, s2;
-        spline_eval<T, Real>(SM, F.off, F.n, q, s, s1, s2);
-        f = F.a * s; f1 = F.a * s1; f2 = F.a * s2;
-    }
-}
-
-/* fn_eval without branches (phase 0b's function slots): the spline is
- * evaluated at the argument clamped to its knots (interval search and
- * coefficients as in spline_eval) and the linear extrapolation, constant and
- * linear kinds are selected; the same values as fn_eval, in one basic block
- * so the slot's dependent LDS loads are not split by branches */
-template <bool BFK, class T, typename Real>
-DEV void fn_eval_bf(const SModel<T, Real> &SM, int fi, Real q, Real &f, Real &f1, Real &f2) {
-    const SFn<Real> &F = SM.fn[fi < 0 ? 0 : fi];
-    const int type = F.type, oo = F.off >= 0 ? F.off : 0, nn = F.n > 1 ? F.n : 1;
-    const Real a = F.a, b = F.b;
-    const Real x0 = SM.kx[oo], xn = SM.kx[oo + nn - 1];
-    const Real qc = q < x0 ? x0 : (q > xn ? xn : q);
-    int k = 0;
-#pragma unroll
-    for (int i = 1; i < T::NKMAX - 1; ++i) {
-        const Real xi = SM.kx[oo + (i < nn - 1 ? i : 0)];
-        k += (i < nn - 1 && qc > xi) ? 1 : 0;
-    }
-    const int j = oo + k, jn = oo + nn - 1;
-    const Real dx = qc - SM.kx[j], kb = SM.kb[j], kc = SM.kc[j], kd = SM.kd[j];
-    Real s0 = SM.ky[j] + dx * (kb + dx * (kc + dx * kd));
-    Real s1 = kb + dx * (Real(2) * kc + Real(3) * dx * kd);
-    Real s2 = Real(2) * kc + Real(6) * dx * kd;
-    const Real ylo = SM.ky[oo], blo = SM.kb[oo], yhi = SM.ky[jn], bhi = SM.kb[jn];
-    const bool lo = q < x0, hi = q > xn;
-    /* every ?: below picks between plain locals: clang emits a ?: whose arms
-     * are expressions as a branch, the loads feeding an arm then sink into
-     * it and the branch can no longer be folded into a select */
-    const bool con = type == BIOIM_FN_CONST, lin = type == BIOIM_FN_LINEAR, present = fi >= 0;
-    if constexpr (BFK) {
-        const Real elo = ylo + (q - x0) * blo, ehi = yhi + (q - xn) * bhi, zero = 0;
-        s0 = lo ? elo : (hi ? ehi : s0);
-        s1 = lo ? blo : (hi ? bhi : s1);
-        s2 = lo || hi ? zero : s2;
-        const Real vl = a * q + b, vs = a * s0, vs1 = a * s1, vs2 = a * s2;
-        f = !present ? zero : (con ? b : (lin ? vl : vs));
-        f1 = !present || con ? zero : (lin ? a : vs1);
-        f2 = !present || con || lin ? zero : vs2;
-    } else {
-        s0 = lo ? ylo + (q - x0) * blo : (hi ? yhi + (q - xn) * bhi : s0);
-        s1 = lo ? blo : (hi ? bhi : s1);
-        s2 = lo || hi ? Real(0) : s2;
-        f = !present ? Real(0) : (con ? b : (lin ? a * q + b : a * s0));
-        f1 = !present || con ? Real(0) : (lin ? a : a * s1);
-        f2 = !present || con || lin ? Real(0) : a * s2;
-    }
-}
-
-/* fn_eval specialised to the function kinds KM (bit kind+1; bit 0 = absent
- * axis) that can occur at this call site (compile-time, per topology axis) */
-template <unsigned KM, class T, typename Real>
-DEV void fn_eval_km(const SModel<T, Real> &SM, int fi, Real q, Real &f, Real &f1, Real &f2) {
-    constexpr bool ABS = (KM & 1u) != 0, CON = (KM & 2u) != 0, LIN = (KM & 4u) != 0, SPL = (KM & 8u) != 0;
-    f = 0; f1 = 0; f2 = 0;
-    if constexpr (!CON && !LIN && !SPL) return;
-    const SFn<Real> &F = SM.fn[ABS ? (fi < 0 ? 0 : fi) : fi];
-    const Real a = F.a, b = F.b;
-    const int type = F.type;
-    Real v = 0, v1 = 0, v2 = 0;
-    if constexpr (LIN && CON) { const bool lin = type == BIOIM_FN_LINEAR; v = lin ? a * q + b : b; v1 = lin ? a : Real(0); }
-    else if constexpr (LIN) { v = a * q + b; v1 = a; }
-    else if constexpr (CON) { v = b; }
-    if constexpr (SPL) {
-        if (type == BIOIM_FN_SPLINE) {
-            Real s0, s1, s2;
-            spline_eval<T, Real>(SM, F.off, F.n, q, s0, s1, s2);
-            v = a * s0; v1 = a * s1; v2 = a * s2;
-        }
-    }
-    const bool present = !ABS || fi >= 0;
-    f = present ? v : Real(0); f1 = present ? v1 : Real(0); f2 = present ? v2 : Real(0);
-}
-
-/* ----------------------------------------------------- smooth curves */
-
-/* a quintic segment in the power basis c[0] + c[1] u + ... + c[5] u^5
- * (converted from the Bezier control points at create time, convert_curve):
- * Horner, 5 FMAs; the derivative 4 */
-template <typename Real> DEV Real bez5(const Real *c, Real u) {
-    return fma(fma(fma(fma(fma(c[5], u, c[4]), u, c[3]), u, c[2]), u, c[1]), u, c[0]);
-}
-template <typename Real> DEV Real dbez5(const Real *c, Real u) {
-    return fma(fma(fma(fma(Real(5) * c[5], u, Real(4) * c[4]), u, Real(3) * c[3]), u, Real(2) * c[2]), u, c[1]);
-}
-
-/* y(x), dy/dx of a SmoothSegmentedFunction.  Branch-free with a fixed trip
- * count (no lane divergence): segment located by comparisons, u(x) started
- * from the segment's 32-interval table by cubic Hermite interpolation (node
- * values ut and slopes mt; start error <= 3.1e-5 over every shipped curve),
- * then Newton steps on the quintic x(u): two reach machine precision in
- * fp64, one is below fp32 rounding (tests/test_curves.py); linear
- * extrapolation outside [x0, x1]. */
-template <bool BF = true, typename Real>
-DEV void curve_eval(const DCurve<Real> &C, Real x, Real &y, Real &dydx) {
-    Real xc = x < C.x0 ? C.x0 : (x > C.x1 ? C.x1 : x);
-    int k = 0;
-#pragma unroll
-    for (int s = 0; s < BIOIM_MAX_CURVESEG - 1; ++s) k += xc > C.xsep[s] ? 1 : 0;
-    Real px[6], py[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) { px[i] = C.cx[k][i]; py[i] = C.cy[k][i]; }
-    Real tt = (xc - C.xa[k]) * C.inv_h[k];
-    int i0 = (int)tt;
-    i0 = i0 < 0 ? 0 : (i0 > BIOIM_UTAB - 1 ? BIOIM_UTAB - 1 : i0);
-    Real fr = tt - Real(i0);
-    /* Hermite basis in the form u0 + f (m0 + f (c2 + f c3)) */
-    const Real u0 = Real(C.ut[k][i0]), u1 = Real(C.ut[k][i0 + 1]), m0 = Real(C.mt[k][i0]), m1 = Real(C.mt[k][i0 + 1]);
-    const Real du = u1 - u0;
-    const Real c2 = Real(3) * du - Real(2) * m0 - m1, c3 = m0 + m1 - Real(2) * du;
-    Real u = fma(fr, fma(fr, fma(fr, c3, c2), m0), u0);
-#pragma unroll
-    for (int it = 0; it < Eps<Real>::curve_newton; ++it) u -= (bez5(px, u) - xc) * newton_rcp(dbez5(px, u));
-    y = bez5(py, u);
-    dydx = dbez5(py, u) * fast_rcp(dbez5(px, u));
-    /* linear extrapolation blended in by 0 / 1 weights (every term finite):
-     * a load under the condition, or a select of loaded values, made the
-     * compiler branch, which split the muscle eval's three independent curve
-     * chains into separate basic blocks */
-    if constexpr (BF) {
-        const Real x0 = C.x0, y0 = C.y0, d0 = C.dydx0, x1 = C.x1, y1 = C.y1, d1 = C.dydx1;
-        const Real ylo = y0 + d0 * (x - x0), yhi = y1 + d1 * (x - x1);
-        const Real wb = x < x0 ? Real(1) : Real(0), wa = x > x1 ? Real(1) : Real(0), wm = Real(1) - wb - wa;
-        y = fma(wb, ylo, fma(wa, yhi, wm * y));
-        dydx = fma(wb, d0, fma(wa, d1, wm * dydx));
-    } else {   /* the branching form: separate blocks, fewer values live at once */
-        if (x < C.x0) { y = C.y0 + C.dydx0 * (x - C.x0); dydx = C.dydx0; }
-        if (x > C.x1) { y = C.y1 + C.dydx1 * (x - C.x1); dydx = C.dydx1; }
-    }
-}
-
-/* root of a*fal*fv(v) + beta*v = rhs (strictly increasing in v), solved in the
- * Bezier parameter of the bracketing segment, warm-started from v0 (the
- * previous substep's root) through the segment's u(x) table; returns v, fv,
- * dfv/dv.  At least two safeguarded Newton steps, then more until
- * converged. */
-template <bool BF = true, bool PE = true, typename Real>
-DEV void solve_fv(const DCurve<Real> &C, Real afal, Real beta, Real rhs, Real v0, Real &v, Real &fv, Real &dfv) {
-    Real g0 = afal * C.y0 + beta * C.x0 - rhs;
-    Real g1 = afal * C.y1 + beta * C.x1 - rhs;
-    int k = 0;
-#pragma unroll
-    for (int s = 1; s < BIOIM_MAX_CURVESEG; ++s) k += afal * C.ya[s] + beta * C.xa[s] - rhs <= 0 ? 1 : 0;
-    Real px[6], py[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) { px[i] = C.cx[k][i]; py[i] = C.cy[k][i]; }
-    const Real xa = C.xa[k], xb = C.xb[k];
-    Real ga = afal * C.ya[k] + beta * xa - rhs, gb = afal * C.yb[k] + beta * xb - rhs;
-    /* both starts computed, one selected (no branch: the table loads and the
-     * division stay in the muscle eval's basic block) — the warm start
-     * through the segment's u(x) table, or the secant of g over the segment */
-    Real u;
-    if constexpr (!BF) {
-        if (v0 > xa && v0 < xb) {
-            Real tt = (v0 - xa) * C.inv_h[k];
-            int i0 = (int)tt;
-            i0 = i0 < 0 ? 0 : (i0 > BIOIM_UTAB - 1 ? BIOIM_UTAB - 1 : i0);
-            Real fr = tt - Real(i0);
-            u = C.ut[k][i0] + fr * (C.ut[k][i0 + 1] - C.ut[k][i0]);
-        } else {
-            u = ga / (ga - gb);
-        }
-    } else {
-        const Real vc = v0 > xa ? (v0 < xb ? v0 : xb) : xa;
-        Real tt = (vc - xa) * C.inv_h[k];
-        int i0 = (int)tt;
-        i0 = i0 < 0 ? 0 : (i0 > BIOIM_UTAB - 1 ? BIOIM_UTAB - 1 : i0);
-        Real fr = tt - Real(i0);
-        const Real ua = C.ut[k][i0], ub = C.ut[k][i0 + 1];
-#if BIOIM_FV_HERMITE
-        /* the cubic Hermite start of curve_eval (table slopes mt) */
-        const Real ma = C.mt[k][i0], mb = C.mt[k][i0 + 1], dua = ub - ua;
-        const Real h2 = Real(3) * dua - Real(2) * ma - mb, h3 = ma + mb - Real(2) * dua;
-        const Real ut = fma(fr, fma(fr, fma(fr, h3, h2), ma), ua), us = ga * newton_rcp(ga - gb);
-#else
-        const Real ut = ua + fr * (ub - ua), us = ga * newton_rcp(ga - gb);
-#endif
-        u = ((v0 > xa) & (v0 < xb)) ? ut : us;
-    }
-    const Real half = 0.5;
-    u = ((u > Real(0)) & (u < Real(1))) ? u : half;
-    /* g(u) = a fal y(u) + beta x(u) - rhs is one quintic in u */
-    Real pg[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) pg[i] = afal * py[i] + beta * px[i];
-    pg[0] -= rhs;
-    Real lo = 0, hi = 1, dprev = 1;
-    /* the root lies past an end of the curve (g keeps one sign over it): the
-     * result is the linear extrapolation below, whatever the loop finds, so
-     * the lane leaves the loop after its first step.  Before round 5 such a
-     * lane ran the Newton loop down to the segment's end by bisections (up to
-     * ~40 iterations) and its wave — and the launch — waited for it: the
-     * raw-action Palsy3D model hit it in 10 % of its waves.
-     * PE: the spatial models only (same-box Palsy3D -15 %, C5 -13 %,
-     * Running3D -1.5 %; the planar kernels, which rarely meet it, measured
-     * +0.5 % with it: profiles/r05/r05k) */
-    const bool past_end = PE && BIOIM_FV_PAST_END && ((g0 >= 0) | (g1 <= 0));
-    for (int it = 0; it < Eps<Real>::it_max; ++it) {
-        Real g = bez5(pg, u);
-        if (g > 0) hi = u; else lo = u;
-        Real dg = dbez5(pg, u);
-        Real un = u - g * newton_rcp(dg);
-        /* inclusive bracket: a converged step (un == u == lo or hi after
-         * rounding) must not trigger the bisection fallback */
-        if (!(un >= lo && un <= hi)) un = Real(0.5) * (lo + hi);
-#ifdef BIOIM_WAVETIME
-        if (!(u - g * newton_rcp(dg) >= lo && u - g * newton_rcp(dg) <= hi) && diag_tid() < BIOIM_WAVETIME_N * 4) g_fvbis[diag_tid()] += 1;
-#endif
-        Real du = fabs(un - u);
-        u = un;
-        /* converged, or stagnating at the rounding level of g */
-        if (past_end || (it >= 1 && (du <= Eps<Real>::u_stop || (du <= Real(1e3) * Eps<Real>::u_tol && du >= Real(0.5) * dprev)))) {
-#ifdef BIOIM_WAVETIME
-            if (diag_tid() < BIOIM_WAVETIME_N * 4) {
-                g_fvit[diag_tid()] += it + 1;
-                if ((unsigned)(it + 1) > g_fvmax[diag_tid()]) g_fvmax[diag_tid()] = it + 1;
-            }
-#endif
-#ifdef BIOIM_STAMPS
-            if (blockIdx.x == 0 && threadIdx.x < 14) atomicAdd(&g_stamps[12], (unsigned long long)(it + 1));
-            if (blockIdx.x == 0 && threadIdx.x < 14) atomicAdd(&g_stamps[13], 1ull);
-#endif
-            break;
-        }
-#ifdef BIOIM_STAMPS
-        if (it == Eps<Real>::it_max - 1 && blockIdx.x == 0 && threadIdx.x < 14) atomicAdd(&g_stamps[14], 1ull);
-#endif
-        dprev = du;
-    }
-    v = bez5(px, u);
-    fv = bez5(py, u);
-    dfv = dbez5(py, u) * fast_rcp(dbez5(px, u));
-    if constexpr (!BF) {
-        if (g0 >= 0) {
-            v = (rhs - afal * (C.y0 - C.dydx0 * C.x0)) / (afal * C.dydx0 + beta);
-            fv = C.y0 + C.dydx0 * (v - C.x0); dfv = C.dydx0;
-        } else if (g1 <= 0) {
-            v = (rhs - afal * (C.y1 - C.dydx1 * C.x1)) / (afal * C.dydx1 + beta);
-            fv = C.y1 + C.dydx1 * (v - C.x1); dfv = C.dydx1;
-        }
-    } else {   /* linear extrapolation past an end (one reciprocal, selected).
-                * Reciprocals instead of IEEE divisions here and in the secant
-                * start: same-box 2D 0.2772 -> 0.2762 ms, 3D 0.5176 -> 0.5145 ms,
-                * C5 unchanged (profiles/r04/r04y; computing this before the
-                * Newton loop instead was 2D -0.6 % but C5 +1.2 %) */
-        const Real y0 = C.y0, d0 = C.dydx0, x0 = C.x0, y1 = C.y1, d1 = C.dydx1, x1 = C.x1;
-        const bool e0 = g0 >= 0, e1 = g1 <= 0;
-        const Real yE = e0 ? y0 : y1, dE = e0 ? d0 : d1, xE = e0 ? x0 : x1;
-        const Real vE = (rhs - afal * (yE - dE * xE)) * fast_rcp(afal * dE + beta);
-        const Real fvE = yE + dE * (vE - xE);
-        const bool ext = e0 | e1;
-        v = ext ? vE : v; fv = ext ? fvE : fv; dfv = ext ? dE : dfv;
-    }
-}
-
-/* publish the coordinate values/speeds to LDS (QF/UF): dof lane d writes its
- * coordinate, lane 0 the locked coordinates (default value, zero speed) */
-template <class T, typename Real>
-DEV void publish_coords(const DModel<Real> &M, const SModel<T, Real> &SM, Real *lds, int lane, Real qd, Real ud) {
-    using LY = Lay<T, Real>;
-    if (lane < T::ND) {
-        const int c = SM.dof_coord[lane];
-        lds[LY::QF + c] = qd;
-        lds[LY::UF + c] = ud;
-    }
-    if (lane == 0) {
-        sfor<0, T::NC>([&](auto cI) {
-            constexpr int c = decltype(cI)::value;
-            if constexpr (T::coord_dof[c] < 0) { lds[LY::QF + c] = M.coord_default[c]; lds[LY::UF + c] = 0; }
-        });
-    }
-}
-
-/* ---------------------------------------------------------- kinematics
- * Phase 1a (lane = composite body c): the joint-local part, which depends
- * only on c's own coordinates — the spatial-transform axes (function
- * values and derivatives, the body-fixed rotation sequence, translations),
- * giving the child-in-parent transform, the joint's relative velocity and
- * velocity-product acceleration in the parent frame, and the joint's
- * Plucker columns about the parent origin (accumulated per dof into SL). */
-
-/* a body's dofs as kin_local meets them: the local slot of (body, axis) is
- * the rank of the axis's dof among the body's distinct dofs in axis order */
-template <class T> struct BodyDofs {
-    static constexpr int dof_of(int b, int ax) {
-        const int co = T::axis_coord[b * 6 + ax];
-        return co >= 0 ? T::coord_dof[co] : -1;
-    }
-    static constexpr int slot(int b, int ax) {
-        const int d = dof_of(b, ax);
-        if (d < 0) return -1;
-        int n = 0;
-        for (int a = 0; a < ax; ++a) {
-            const int e = dof_of(b, a);
-            if (e < 0) continue;
-            bool seen = false;
-            for (int a2 = 0; a2 < a; ++a2) seen = seen || dof_of(b, a2) == e;
-            if (e == d) return n;
-            n += seen ? 0 : 1;
-        }
-        return n;
-    }
-    static constexpr int count(int b) {
-        int n = 0;
-        for (int ax = 0; ax < 6; ++ax) n = slot(b, ax) + 1 > n ? slot(b, ax) + 1 : n;
-        return n;
-    }
-    static constexpr int max_count() {
-        int n = 1;
-        for (int b = 0; b < T::NB; ++b) n = count(b) > n ? count(b) : n;
-        return n;
-    }
-    static constexpr int dof(int b, int k) {
-        for (int ax = 0; ax < 6; ++ax)
-            if (slot(b, ax) == k) return dof_of(b, ax);
-        return -1;
-    }
-    /* every dof is a local dof of exactly one body (its SL row has one writer) */
-    static constexpr bool covers_all() {
-        for (int d = 0; d < T::ND; ++d) {
-            int n = 0;
-            for (int b = 0; b < T::NB; ++b)
-                for (int k = 0; k < count(b); ++k) n += dof(b, k) == d ? 1 : 0;
-            if (n != 1) return false;
-        }
-        return true;
-    }
-};
-
-template <class T, typename Real, int FE = 0>
-DEV void kin_local(const SModel<T, Real> &SM, Real *lds, int c) {
-    using LY = Lay<T, Real>;
-    using PL = Planar<T>;
-    constexpr unsigned ZR = PL::ZR, ZW = PL::ZW, ZV = PL::ZV;
-    constexpr unsigned USED = TopoInfo<T>::axes_used();
-    const SBody<Real> &b = SM.body[c];
-    Real RFM[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    Real wrel[3] = {0, 0, 0}, arel[3] = {0, 0, 0}, pFM[3] = {0, 0, 0}, pd[3] = {0, 0, 0}, pdd[3] = {0, 0, 0};
-    Real col[6][3];
-    int cd[6];   /* the axis's dof; FE_COLS: its local slot (BodyDofs) */
-    sfor<0, 6>([&](auto aI) {
-        constexpr int ax = decltype(aI)::value;
-        cd[ax] = -1;
-        if constexpr (((USED >> ax) & 1u) != 0) {
-            /* the axis function's kind, coordinate, dof and spline slot are
-             * compile-time facts of (body, axis) (topology_matches checks kind
-             * and coordinate per pack): selected by the lane instead of read
-             * through the function table, so the coordinate and coefficient
-             * loads do not wait on one another */
-            int kind = -1, cc = -1, dof = -1, js = -1;
-            /* spatial models: an opaque copy of the lane's body, so the
-             * selects are recomputed per call (a few VALU ops) instead of
-             * hoisted out of the substep loop into 24 registers live across
-             * it (the 3D push + RK-Merson kernel otherwise spills 16 B; 1 %
-             * slower in 3D, so the planar kernels, far from the register
-             * limit, keep the hoisted copies) */
-            int cb = c;
-            if constexpr (!T::PLANAR) asm volatile("" : "+v"(cb));
-            sfor<0, T::NB>([&](auto bI) {
-                constexpr int bb = decltype(bI)::value;
-                constexpr int k = T::axis_kind[bb * 6 + ax], co = T::axis_coord[bb * 6 + ax];
-                constexpr int dc = co >= 0 ? T::coord_dof[co] : -1, jsl = TopoInfo<T>::jslot(bb, ax);
-                kind = cb == bb ? k : kind;
-                cc = cb == bb ? co : cc;
-                constexpr int dl = (FE & FE_COLS) ? BodyDofs<T>::slot(bb, ax) : dc;
-                dof = cb == bb ? dl : dof;
-                js = cb == bb ? jsl : js;
-            });
-            const int cs = cc >= 0 ? cc : 0;
-            Real qc = lds[LY::QF + cs], uc = lds[LY::UF + cs];
-            qc = cc >= 0 ? qc : Real(0);
-            uc = cc >= 0 ? uc : Real(0);
-            constexpr unsigned KM = TopoInfo<T>::axis_kinds(ax);
-            const Real fa = b.fa[ax], fb = b.fb[ax];
-            Real f = 0, f1 = 0, f2 = 0;
-            if constexpr ((FE & FE_KINDS) && T::PLANAR) {
-                /* both forms from the loads above, selected */
-                if constexpr ((KM & (1u << (BIOIM_FN_LINEAR + 1))) != 0) {
-                    const bool li = kind == BIOIM_FN_LINEAR;
-                    const Real lf = fa * qc + fb;
-                    f = li ? lf : f; f1 = li ? fa : f1;
-                }
-                if constexpr ((KM & (1u << (BIOIM_FN_CONST + 1))) != 0) f = kind == BIOIM_FN_CONST ? fb : f;
-            } else {
-                if constexpr ((KM & (1u << (BIOIM_FN_LINEAR + 1))) != 0) {
-                    if (kind == BIOIM_FN_LINEAR) { f = fa * qc + fb; f1 = fa; }
-                }
-                if constexpr ((KM & (1u << (BIOIM_FN_CONST + 1))) != 0) {
-                    if (kind == BIOIM_FN_CONST) f = fb;
-                }
-            }
-            if constexpr ((KM & (1u << (BIOIM_FN_SPLINE + 1))) != 0) {
-                /* spline axes: evaluated in phase 0b.  Planar: loaded
-                 * unconditionally (slot 0 for the other kinds) and selected,
-                 * no branch (same-box Torque2D -3 %, 2D -0.7 % with the
-                 * branch-free SL and subtree sums; no gain in 3D, where it
-                 * costs registers: profiles/r03/ab_subtree.txt) */
-                const int jj = js >= 0 ? js : 0;
-                if constexpr (T::PLANAR) {
-                    const bool sp = kind == BIOIM_FN_SPLINE;
-                    const Real sf = lds[LY::MF + 3 * jj], sf1 = lds[LY::MF + 3 * jj + 1], sf2 = lds[LY::MF + 3 * jj + 2];
-                    f = sp ? sf : f; f1 = sp ? sf1 : f1; f2 = sp ? sf2 : f2;
-                } else if (kind == BIOIM_FN_SPLINE) {
-                    f = lds[LY::MF + 3 * jj]; f1 = lds[LY::MF + 3 * jj + 1]; f2 = lds[LY::MF + 3 * jj + 2];
-                }
-            }
-            cd[ax] = dof;
-            Real a[3] = {b.axis[ax][0], b.axis[ax][1], b.axis[ax][2]};
-            if constexpr (ax < 3) {
-                PL::ang(a);
-                Real ucol[3], cr[3];
-                mv3m<ZR, ZW>(RFM, a, ucol);
-                Real thd = f1 * uc;
-                cross3m<ZW, ZW>(wrel, ucol, cr);
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    arel[i] += ucol[i] * (f2 * uc * uc) + cr[i] * thd;
-                    wrel[i] += ucol[i] * thd;
-                    col[ax][i] = ucol[i] * f1;
-                }
-                PL::ang(arel); PL::ang(wrel); PL::ang(col[ax]);
-                Real Rk[9];
-                if constexpr (T::PLANAR) {   /* about (0, 0, a_z), a_z = +-1 */
-                    Real sn, cn;
-                    sincos_rt(f, sn, cn);
-                    Rk[0] = cn; Rk[1] = -sn * a[2]; Rk[3] = sn * a[2]; Rk[4] = cn;
-                    PL::rot(Rk);
-                } else {
-                    axis_rot(a, f, Rk);  /* f == 0 (absent axis): identity */
-                }
-                mm3m<ZR, ZR>(RFM, Rk, RFM);
-            } else {
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    pFM[i] += a[i] * f; pd[i] += a[i] * (f1 * uc); pdd[i] += a[i] * (f2 * uc * uc);
-                    col[ax][i] = a[i] * f1;
-                }
-                PL::lin(pd); PL::lin(pdd); PL::lin(col[ax]);
-            }
-        }
-    });
-    Real Rpf[9], Rmb[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) { Rpf[i] = b.R_pf[i]; Rmb[i] = b.R_mb[i]; }
-    PL::rot(Rpf); PL::rot(Rmb);
-    Real dF[3], T9[9], RPB[9], pm[3], pPB[3];
-    mv3m<ZR, 0>(RFM, b.p_mb, dF);
-    mm3m<ZR, ZR>(Rpf, RFM, T9);
-    mm3m<ZR, ZR>(T9, Rmb, RPB);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) pm[i] = pFM[i] + dF[i];
-    mv3m<ZR, 0>(Rpf, pm, pPB);
-    Real *lc = lds + LY::LOC + 24 * c;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) lc[i] = RPB[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) lc[9 + i] = pPB[i] + b.p_pf[i];
-    Real t1[3], t2[3], t3[3], o[3];
-    mv3m<ZR, ZW>(Rpf, wrel, o);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) lc[12 + i] = o[i];
-    cross3m<ZW, 0>(wrel, dF, t1);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) t2[i] = pd[i] + t1[i];
-    mv3m<ZR, ZV>(Rpf, t2, o);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) lc[15 + i] = o[i];
-    mv3m<ZR, ZW>(Rpf, arel, o);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) lc[18 + i] = o[i];
-    cross3m<ZW, 0>(arel, dF, t2);
-    cross3m<ZW, ZV>(wrel, t1, t3);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) t2[i] = pdd[i] + t2[i] + t3[i];
-    mv3m<ZR, ZV>(Rpf, t2, o);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) lc[21 + i] = o[i];
-    /* Plucker columns in the parent frame, linear part at the parent origin;
-     * rotations act about the M origin pM = p_pf + R_pf pFM */
-    Real pM[3];
-    mv3m<ZR, 0>(Rpf, pFM, pM);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) pM[i] += b.p_pf[i];
-    if constexpr ((FE & FE_COLS) != 0) {
-        /* per local dof slot k: 0 + the contributions of the axes that move
-         * it, in axis order (selects; an axis without a dof matches no slot),
-         * then one plain store of the dof's words */
-        constexpr int NLS = BodyDofs<T>::max_count();
-        static_assert(BodyDofs<T>::covers_all(), "FE_COLS: one body lane stores each dof's SL row");
-        Real acc[NLS][6];
-#pragma unroll
-        for (int k = 0; k < NLS; ++k)
-#pragma unroll
-            for (int i = 0; i < 6; ++i) acc[k][i] = 0;
-        sfor<0, 6>([&](auto aI) {
-            constexpr int ax = decltype(aI)::value;
-            if constexpr (((USED >> ax) & 1u) != 0) {
-                Real v[3], lin[3] = {0, 0, 0};
-                if constexpr (ax < 3) {
-                    mv3m<ZR, ZW>(Rpf, col[ax], v);
-                    cross3m<0, ZW>(pM, v, lin);
-                } else {
-                    mv3m<ZR, ZV>(Rpf, col[ax], v);
-                }
-#pragma unroll
-                for (int k = 0; k < NLS; ++k) {
-                    const bool on = cd[ax] == k;
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) {
-                        if constexpr (ax < 3) {
-                            if (!((ZW >> i) & 1u)) acc[k][i] = on ? acc[k][i] + v[i] : acc[k][i];
-                            if (!((ZV >> i) & 1u)) acc[k][3 + i] = on ? acc[k][3 + i] + lin[i] : acc[k][3 + i];
-                        } else {
-                            if (!((ZV >> i) & 1u)) acc[k][3 + i] = on ? acc[k][3 + i] + v[i] : acc[k][3 + i];
-                        }
-                    }
-                }
-            }
-        });
-        int cb = c;
-        if constexpr (!T::PLANAR) asm volatile("" : "+v"(cb));
-        sfor<0, NLS>([&](auto kI) {
-            constexpr int k = decltype(kI)::value;
-            int dk = -1;
-            sfor<0, T::NB>([&](auto bI) {
-                constexpr int bb = decltype(bI)::value;
-                constexpr int dbk = BodyDofs<T>::dof(bb, k);
-                dk = cb == bb ? dbk : dk;
-            });
-            if (dk >= 0) {
-                Real *sl = lds + LY::SL + 6 * dk;
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    if (!((ZW >> i) & 1u)) sl[i] = acc[k][i];
-                    if (!((ZV >> i) & 1u)) sl[3 + i] = acc[k][3 + i];
-                }
-            }
-        });
-    } else
-    sfor<0, 6>([&](auto aI) {
-        constexpr int ax = decltype(aI)::value;
-        if constexpr (((USED >> ax) & 1u) != 0) {
-            /* planar: an axis without a dof accumulates into the sink row
-             * SL[ND] (no branch) */
-            if (T::PLANAR || cd[ax] >= 0) {
-                Real *sl = lds + LY::SL + 6 * (cd[ax] >= 0 ? cd[ax] : LY::ND);
-                Real v[3];
-                if constexpr (ax < 3) {
-                    mv3m<ZR, ZW>(Rpf, col[ax], v);
-                    Real lin[3];
-                    cross3m<0, ZW>(pM, v, lin);
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) {
-                        if (!((ZW >> i) & 1u)) sl[i] += v[i];
-                        if (!((ZV >> i) & 1u)) sl[3 + i] += lin[i];
-                    }
-                } else {
-                    mv3m<ZR, ZV>(Rpf, col[ax], v);
-#pragma unroll
-                    for (int i = 0; i < 3; ++i)
-                        if (!((ZV >> i) & 1u)) sl[3 + i] += v[i];
-                }
-            }
-        }
-    });
-}
-
-/* body frame and motion: orientation, origin, angular velocity, spatial
- * velocity at the (shifted) ground origin, and the velocity-product
- * accelerations (zero q'') */
-template <typename Real> struct Frame {
-    Real R[9], o[3], w[3], vO[3], al[3], aO[3];
-};
-
-/* F := F composed with the joint whose parent-frame data is lc (LOC slot).
- * Zero masks: R rotations, w/wrg/al angular, vO/vrel/aO/aa linear (Planar) */
-template <class T, typename Real> DEV void compose(Frame<Real> &F, const Real *lc) {
-    using PL = Planar<T>;
-    constexpr unsigned ZR = PL::ZR, ZW = PL::ZW, ZV = PL::ZV;
-    Real R[9], oB[3], w[3], wrg[3], vrel[3], vO[3], al[3], t[3], t2[3], t3[3];
-    mm3m<ZR, ZR>(F.R, lc, R);
-    mv3m<ZR, 0>(F.R, lc + 9, t);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) oB[i] = F.o[i] + t[i];
-    mv3m<ZR, ZW>(F.R, lc + 12, wrg);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) w[i] = F.w[i] + wrg[i];
-    mv3m<ZR, ZV>(F.R, lc + 15, vrel);
-    cross3m<ZW, 0>(wrg, oB, t);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) vO[i] = F.vO[i] + vrel[i] - t[i];
-    mv3m<ZR, ZW>(F.R, lc + 18, t);
-    cross3m<ZW, ZW>(F.w, wrg, t2);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) al[i] = F.al[i] + t2[i] + t[i];
-    /* acceleration of the new origin: parent point acceleration
-     * + Coriolis 2 wP x vrel + relative acceleration */
-    Real vpt[3], aB[3], aa[3];
-    cross3m<ZW, 0>(F.w, oB, t);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) vpt[i] = F.vO[i] + t[i];
-    cross3m<ZW, 0>(F.al, oB, t);
-    cross3m<ZW, ZV>(F.w, vpt, t2);
-    cross3m<ZW, ZV>(F.w, vrel, t3);
-    mv3m<ZR, ZV>(F.R, lc + 21, aa);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) aB[i] = F.aO[i] + t[i] + t2[i] + Real(2) * t3[i] + aa[i];
-    Real vB[3];
-    cross3m<ZW, 0>(w, oB, t);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) vB[i] = vO[i] + t[i];
-    cross3m<ZW, 0>(al, oB, t);
-    cross3m<ZW, ZV>(w, vB, t2);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) F.R[i] = R[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        F.aO[i] = aB[i] - t[i] - t2[i];
-        F.o[i] = oB[i]; F.w[i] = w[i]; F.vO[i] = vO[i]; F.al[i] = al[i];
-    }
-    PL::rot(F.R); PL::ang(F.w); PL::lin(F.vO); PL::ang(F.al); PL::lin(F.aO);
-}
-
-/* FE_LEVEL0: compose() for the chain's first level, whose F is the ground
- * frame (R = I, o = (-x0, 0, 0), no motion): the same values without the
- * products with those constants (equal for finite inputs up to the sign of a
- * zero) */
-template <class T, typename Real> DEV void compose_ground(Frame<Real> &F, const Real *lc, Real x0) {
-    using PL = Planar<T>;
-    constexpr unsigned ZW = PL::ZW, ZV = PL::ZV;
-    Real oB[3], vB[3], t[3], t2[3];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) F.R[i] = lc[i];
-    oB[0] = lc[9] - x0; oB[1] = lc[10]; oB[2] = lc[11];
-    const Real *wrg = lc + 12, *vrel = lc + 15, *al = lc + 18, *aa = lc + 21;
-    cross3m<ZW, 0>(wrg, oB, t);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { F.o[i] = oB[i]; F.w[i] = wrg[i]; F.vO[i] = vrel[i] - t[i]; F.al[i] = al[i]; }
-    cross3m<ZW, 0>(F.w, oB, t);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) vB[i] = F.vO[i] + t[i];
-    cross3m<ZW, 0>(al, oB, t);
-    cross3m<ZW, ZV>(F.w, vB, t2);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) F.aO[i] = aa[i] - t[i] - t2[i];
-    PL::rot(F.R); PL::ang(F.w); PL::lin(F.vO); PL::ang(F.al); PL::lin(F.aO);
-}
-
-/* identity joint (LOC slot NB) and the ground frame (KB/AL slot NB) */
-template <class T, typename Real> DEV constexpr bool ground_loc_free() {
-    using LY = Lay<T, Real>;
-    return LY::LOC + 24 * T::NB >= LY::TAU + LY::TAUN && LY::LOC + 24 * T::NB >= LY::CJ + LY::NS * LY::CJN;
-}
-template <class T, typename Real> DEV void kin_ground_loc(Real *lds) {
-    Real *lc = lds + Lay<T, Real>::LOC + 24 * T::NB;
-#pragma unroll
-    for (int i = 0; i < 24; ++i) lc[i] = (i < 9 && (i % 4) == 0) ? Real(1) : Real(0);
-}
-template <class T, typename Real> DEV void kin_ground_const(Real *lds) {
-    using LY = Lay<T, Real>;
-    Real *kb = lds + LY::KB + 18 * T::NB, *ab = lds + LY::AL + 6 * T::NB;
-#pragma unroll
-    for (int i = 0; i < 18; ++i) kb[i] = (i < 9 && (i % 4) == 0) ? Real(1) : Real(0);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) ab[i] = 0;
-}
-template <class T, typename Real, bool ONCE = false> DEV void kin_ground(Real *lds, Real x0) {
-    if constexpr (!ONCE || !ground_loc_free<T, Real>()) kin_ground_loc<T, Real>(lds);
-    if constexpr (!ONCE) kin_ground_const<T, Real>(lds);
-    lds[Lay<T, Real>::KB + 18 * T::NB + 9] = -x0;
-}
-
-/* Phase 1b (lane = body c): compose c's root-to-body joint chain in
- * registers (front-padded with the identity joint, so every lane runs the
- * same DEPTH compositions with no inter-lane dependency) */
-template <class T, typename Real, int FE = 0>
-DEV void kin_chain(const SModel<T, Real> &SM, Real *lds, int c, Real x0, Frame<Real> &F) {
-    using LY = Lay<T, Real>;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) F.R[i] = (i % 4) == 0 ? Real(1) : Real(0);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { F.o[i] = i == 0 ? -x0 : Real(0); F.w[i] = 0; F.vO[i] = 0; F.al[i] = 0; F.aO[i] = 0; }
-    sfor<0, TopoInfo<T>::depth()>([&](auto lI) {
-        constexpr int lvl = decltype(lI)::value;
-        const Real *src = lds + LY::LOC + 24 * SM.chain[c][lvl];
-        Real lc[24];
-#pragma unroll
-        for (int i = 0; i < 24; ++i) lc[i] = src[i];
-        Planar<T>::loc(lc);
-        if constexpr (lvl == 0 && (FE & FE_LEVEL0) != 0) compose_ground<T, Real>(F, lc, x0);
-        else compose<T, Real>(F, lc);
-    });
-    Real *kb = lds + LY::KB + 18 * c, *ab = lds + LY::AL + 6 * c;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) kb[i] = F.R[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        kb[9 + i] = F.o[i]; kb[12 + i] = F.w[i]; kb[15 + i] = F.vO[i];
-        ab[i] = F.al[i]; ab[3 + i] = F.aO[i];
-    }
-}
-template <class T, typename Real>
-DEV void kin_chain(const SModel<T, Real> &SM, Real *lds, int c, Real x0) {
-    Frame<Real> F;
-    kin_chain<T, Real>(SM, lds, c, x0, F);
-}
-
-/* Phase 0b: the function slots (Lay::MF), one lane each — moving path
- * points' location functions and the joints' spline axes — from the
- * published coordinates; ends with a wave sync when there are any */
-template <bool BFK, class T, typename Real>
-DEV void fn_slots(const SModel<T, Real> &SM, Real *lds, int lane) {
-    using LY = Lay<T, Real>;
-    if constexpr (LY::NSLOT > 0) {
-        sfor<0, (LY::NSLOT + T::G - 1) / T::G>([&](auto pI) {
-            const int f = lane + decltype(pI)::value * T::G;
-            if (f < LY::NSLOT) {
-                Real v, d1, d2;
-                fn_eval_bf<BFK, T, Real>(SM, SM.mf_fn[f], lds[LY::QF + SM.mf_coord[f]], v, d1, d2);
-                lds[LY::MF + 3 * f] = v;
-                lds[LY::MF + 3 * f + 1] = d1;
-                lds[LY::MF + 3 * f + 2] = d2;
-            }
-        });
-        wave_sync();
-    }
-}
-
-/* Phase 1c (lane = dof): ground Plucker column from the parent frame */
-template <class T, typename Real>
-DEV void kin_column(const SModel<T, Real> &SM, Real *lds, int d) {
-    using LY = Lay<T, Real>;
-    using PL = Planar<T>;
-    constexpr unsigned ZR = PL::ZR, ZW = PL::ZW, ZV = PL::ZV;
-    const Real *kp = lds + LY::KB + 18 * SM.body[SM.dof_cb[d]].pslot;
-    const Real *sl = lds + LY::SL + 6 * d;
-    Real K[12], sc[6];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) K[i] = kp[i];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) sc[i] = sl[i];
-    PL::rot(K); PL::col(sc);
-    Real Sa[3], Sl[3], t[3];
-    mv3m<ZR, ZW>(K, sc, Sa);
-    mv3m<ZR, ZV>(K, sc + 3, Sl);
-    cross3m<ZW, 0>(Sa, K + 9, t);
-    Real *S = lds + LY::S + 6 * d;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { S[i] = Sa[i]; S[3 + i] = Sl[i] - t[i]; }
-}
-
-/* Phase 1c (lane = body): spatial inertia at the ground origin and the
- * Newton-Euler (velocity-product + gravity) wrench */
-template <class T, typename Real, bool FROM_FRAME = false>
-DEV void body_inertia(const SModel<T, Real> &SM, const DModel<Real> &M, Real *lds, int c, const Frame<Real> *F = nullptr) {
-    using LY = Lay<T, Real>;
-    using PL = Planar<T>;
-    constexpr unsigned ZR = PL::ZR, ZW = PL::ZW, ZV = PL::ZV;
-    const SBody<Real> &b = SM.body[c];
-    const Real *kb = lds + LY::KB + 18 * c, *ab = lds + LY::AL + 6 * c;
-    Real K[18], A[6];
-    if constexpr (FROM_FRAME) {   /* FE_INERTIA: the frame kin_chain left in the lane's registers */
-#pragma unroll
-        for (int i = 0; i < 9; ++i) K[i] = F->R[i];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            K[9 + i] = F->o[i]; K[12 + i] = F->w[i]; K[15 + i] = F->vO[i];
-            A[i] = F->al[i]; A[3 + i] = F->aO[i];
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < 18; ++i) K[i] = kb[i];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) A[i] = ab[i];
-    }
-    PL::frame(K); PL::acc(A);
-    const Real *R = K, *o = K + 9, *w = K + 12, *vO = K + 15, *al = A, *aO = A + 3;
-    Real cl[3], cG[3];
-    mv3m<ZR, 0>(R, b.com, cl);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) cG[i] = o[i] + cl[i];
-    Real Ib[9] = {b.inertia[0], b.inertia[3], b.inertia[4], b.inertia[3], b.inertia[1],
-                  b.inertia[5], b.inertia[4], b.inertia[5], b.inertia[2]};
-    Real Tm[9], RT[9], IG[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) RT[3 * i + j] = R[3 * j + i];
-    mm3m<ZR, 0>(R, Ib, Tm);
-    mm3m<0, ZR>(Tm, RT, IG);
-    Real m = b.mass, ccd = dot3(cG, cG);
-    Real *ic = lds + LY::IC + 10 * c;
-    ic[0] = m;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) ic[1 + i] = m * cG[i];
-    ic[4] = IG[0] + m * (ccd - cG[0] * cG[0]);
-    ic[5] = IG[4] + m * (ccd - cG[1] * cG[1]);
-    ic[6] = IG[8] + m * (ccd - cG[2] * cG[2]);
-    ic[7] = IG[1] - m * cG[0] * cG[1];
-    ic[8] = IG[2] - m * cG[0] * cG[2];
-    ic[9] = IG[5] - m * cG[1] * cG[2];
-    Real vc[3], ac[3], t[3], t2[3];
-    cross3m<ZW, 0>(w, cG, t);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) vc[i] = vO[i] + t[i];
-    cross3m<ZW, 0>(al, cG, t);
-    cross3m<ZW, ZV>(w, vc, t2);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) ac[i] = aO[i] + t[i] + t2[i];
-    Real f[3], Iw[3], Ia[3], n[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) f[i] = m * (ac[i] - M.gravity[i]);
-    mv3m<0, ZW>(IG, w, Iw);
-    mv3m<0, ZW>(IG, al, Ia);
-    cross3m<ZW, 0>(w, Iw, t);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) n[i] = Ia[i] + t[i];
-    cross3(cG, f, t);
-    Real *wb = lds + LY::WB + 6 * c;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { wb[i] = n[i] + t[i]; wb[3 + i] = f[i]; }
-}
+#include "bioim_curves.h"
+#include "bioim_kinematics.h"
 
 /* ---------------------------------------------------- contact + limits */
 

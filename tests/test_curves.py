@@ -1,6 +1,6 @@
 """The device path inverts x(u) of each quintic Bezier segment from a
 32-interval u(x) table (node values and slopes, cubic Hermite start) and a
-fixed number of Newton steps: two in fp64, one in fp32 (bioim_step.hip
+fixed number of Newton steps: two in fp64, one in fp32 (bioim_curves.h
 curve_eval).  Verify that this scheme reaches machine precision in fp64 and
 stays below fp32 rounding in one step, on every segment of every curve of
 every built pack (host restatement of the scheme)."""

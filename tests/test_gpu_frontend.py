@@ -1,5 +1,5 @@
 """The kinematics front end of the step kernels' dynamics call
-(csrc/bioim_step.hip, BIOIM_FRONTEND: joint columns summed in registers,
+(csrc/bioim_kinematics.h, BIOIM_FRONTEND: joint columns summed in registers,
 branch-free axis kinds in the planar joint-local kinematics, the chain's frame
 handed to the inertias in registers, the first chain level composed from the
 ground frame), and the force elements that read what it publishes (the
