@@ -167,6 +167,32 @@ DEV size_t bioim_chk(size_t i, size_t n, const char *file, int line) {
 #endif
 constexpr int FE_COLS = 1, FE_KINDS = 2, FE_INERTIA = 4, FE_LEVEL0 = 8;
 
+/* BIOIM_LANEIDX (the step kernels' dynamics calls; the analysis kernels and
+ * state_kinematics call the helpers without a record, the forms below without
+ * it): the small integers a lane reads from the model image in every call —
+ * body slots, gather lists, path point numbers, which depend on the lane
+ * alone — are read once per launch into a packed per-lane record (LaneIdx,
+ * bioim_kinematics.h) that stays in registers; a call unpacks them with a
+ * bit-field extract instead of a dependent LDS round trip.  Only loads and
+ * integer arithmetic go; every floating-point operation and its order stay.
+ * One bit per consumer:
+ *   1 (LI_COLS)   kin_column's parent-frame offset, phase 3's body (WB, IC)
+ *   2 (LI_TAU)    the dof lane's TAU gather list (phase 3 and the cached first
+ *                 substep), its limit mask, the limit lane's coordinate
+ *   4 (LI_PATH)   muscle_path: the muscle's point offset and count, its span,
+ *                 each point slot's frame, and the conditional / moving slots'
+ *                 flags, coordinate and function slots
+ * One byte per kernel family, as BIOIM_FRONTEND.  Shipped (same-box A/B,
+ * DESIGN.md 9): all three in the planar kernels; the spatial and the fused byte
+ * are 0 (not measured there), the RK kernels take none (TailSwitch), and
+ * those kernels are unchanged.  Two more bits were measured and taken out:
+ * the muscle curves' base offsets (slower) and the function slots' numbers
+ * (inside the spread). */
+#ifndef BIOIM_LANEIDX
+#define BIOIM_LANEIDX 0x000007
+#endif
+constexpr int LI_COLS = 1, LI_TAU = 2, LI_PATH = 4;
+
 /* BIOIM_GROUND_ONCE (the step kernels): the ground slot's constants — the KB
  * rotation, its zero origin / velocity words and the zero AL row, which no
  * other code writes — go to LDS once per launch (kin_ground_const) and a call

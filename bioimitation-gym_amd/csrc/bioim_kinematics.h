@@ -13,6 +13,123 @@
 #include "bioim_math.h"
 #include "topologies.h"
 
+/* ------------------------------------------------- the per-lane index record
+ * BIOIM_LANEIDX: what a lane reads from the model image's index tables in
+ * every dynamics call, read once per launch (lane_index, env_block's prologue;
+ * a fused rollout runs that prologue, image staging included, once per step)
+ * and kept packed in registers.  A lane past a count (no dof, limit or muscle
+ * of its own) carries element 0's values, or an empty mask: the
+ * calls read those fields only under the same lane conditions as before.
+ * Field widths are checked against the topology where a bit is on. */
+DEV constexpr uint32_t li_bits(uint32_t w, int pos, int n) { return (w >> pos) & ((1u << n) - 1u); }
+template <class T, typename Real> struct LaneIdx {
+    using LY = Lay<T, Real>;
+    static constexpr int MPL = LY::MPL, MP = T::MAXPT > 0 ? T::MAXPT : 1;
+    static constexpr int NTW = (T::MAXARM + 3) / 4;
+    /* LI_COLS: bits 0-15 the LDS word offset of the parent frame of the lane's
+     * dof (KB + 18 pslot), 16-23 the dof's body */
+    uint32_t cols;
+    /* LI_TAU: the dof's TAU gather list, a byte per entry; lim: bits 0-7 the
+     * limit lane's coordinate, bit 8 + li set where limit li acts on the dof */
+    uint32_t tau[NTW], lim;
+    /* LI_PATH, per muscle slot.  path: bits 0-7 pt_off, 8-11 npt, 12-15 nspan,
+     * 16 + 4k the span's dof k (0 past nspan).  frame: 4 bits per point slot,
+     * its body (point 0's past npt).  pt[j], the slots PT_COND / PT_MOVING
+     * allow: bit 0 conditional, 1-5 its coordinate (0: not conditional),
+     * bit 6 moving, 8 + 6a the function slot of axis a (5 bits; 0 and bit 5
+     * set: none, the point's own location) */
+    uint32_t path[MPL], frame[MPL], pt[MPL][MP];
+
+    /* the record as one dynamics call reads it: the words in use made opaque,
+     * so that the call's unpacked values and the addresses formed from them
+     * are computed in the call (a shift and a mask) and not hoisted out of the
+     * substep loop into registers of their own (LI_PATH alone took 21 more
+     * registers that way, and the set put the Muscle2D kernels on scratch) */
+    template <int LI> DEV LaneIdx call_copy() const {
+        LaneIdx c = *this;
+        auto hide = [](uint32_t &w) { asm volatile("" : "+v"(w)); };
+        if constexpr ((LI & LI_COLS) != 0) hide(c.cols);
+        if constexpr ((LI & LI_TAU) != 0) {
+#pragma unroll
+            for (int i = 0; i < NTW; ++i) hide(c.tau[i]);
+            hide(c.lim);
+        }
+#pragma unroll
+        for (int j = 0; j < MPL; ++j) {
+            if constexpr ((LI & LI_PATH) != 0 && T::NM > 0) {
+                hide(c.path[j]); hide(c.frame[j]);
+                sfor<0, MP>([&](auto pI) {
+                    constexpr int p = decltype(pI)::value;
+                    if constexpr ((((T::PT_COND | T::PT_MOVING) >> p) & 1u) != 0) hide(c.pt[j][p]);
+                });
+            }
+        }
+        return c;
+    }
+    DEV int kp() const { return (int)li_bits(cols, 0, 16); }
+    DEV int body() const { return (int)li_bits(cols, 16, 8); }
+    DEV int tau_src(int i) const { return (int)li_bits(tau[i / 4], 8 * (i % 4), 8); }
+    DEV int lim_coord() const { return (int)li_bits(lim, 0, 8); }
+    DEV bool lim_mine(int li) const { return ((lim >> (8 + li)) & 1u) != 0; }
+};
+
+template <int LI, class T, typename Real>
+DEV void lane_index(const SModel<T, Real> &SM, int lane, LaneIdx<T, Real> &I) {
+    using LY = Lay<T, Real>;
+    using IX = LaneIdx<T, Real>;
+    if constexpr ((LI & LI_COLS) != 0) {
+        static_assert(LY::KB + 18 * (T::NB + 1) < 65536 && T::NB < 256, "LI_COLS field widths");
+        const int cb = SM.dof_cb[lane < LY::ND ? lane : 0];
+        I.cols = (uint32_t)(LY::KB + 18 * SM.body[cb].pslot) | ((uint32_t)cb << 16);
+    }
+    if constexpr ((LI & LI_TAU) != 0) {
+        static_assert(T::NC < 256 && T::NL <= 24, "LI_TAU field widths");
+        const int d = lane < LY::ND ? lane : 0;
+#pragma unroll
+        for (int i = 0; i < IX::NTW; ++i) I.tau[i] = 0;
+#pragma unroll
+        for (int i = 0; i < T::MAXARM; ++i) I.tau[i / 4] |= (uint32_t)SM.tau_src[d][i] << (8 * (i % 4));
+        uint32_t w = (uint32_t)SM.lim_coord[lane < T::NL ? lane : 0];
+#pragma unroll
+        for (int li = 0; li < T::NL; ++li) w |= (SM.lim_dof[li] == lane ? 1u : 0u) << (8 + li);
+        I.lim = w;
+    }
+    if constexpr ((LI & LI_PATH) != 0 && T::NM > 0) {
+        sfor<0, IX::MPL>([&](auto jI) {
+            constexpr int j = decltype(jI)::value;
+            const int m = mslot<T>(lane + j * T::G);
+            const SMuscle<Real> &mu = SM.mus[m < T::NM ? m : 0];
+            static_assert(T::NPT < 256 && T::MAXPT <= 8 && T::MAXSPAN <= 4 && LY::ND <= 16 && T::NB < 16 && T::NC <= 32 && LY::NSLOT <= 32,
+                          "LI_PATH field widths");
+            const int po = mu.pt_off, npt = mu.npt, nsp = mu.nspan;
+            uint32_t w = (uint32_t)po | (uint32_t)npt << 8 | (uint32_t)nsp << 12, fw = 0;
+#pragma unroll
+            for (int k = 0; k < T::MAXSPAN; ++k) w |= (uint32_t)(k < nsp ? mu.span[k] : 0) << (16 + 4 * k);
+            I.path[j] = w;
+            sfor<0, IX::MP>([&](auto pI) {
+                constexpr int p = decltype(pI)::value;
+                const DPathPt<Real> &pt = SM.pt[po + (p < npt ? p : 0)];
+                fw |= (uint32_t)pt.cbody << (4 * p);
+                uint32_t pw = 0;
+                if constexpr (((T::PT_COND >> p) & 1u) != 0) {
+                    const bool cnd = pt.type == BIOIM_PT_COND;
+                    pw |= (cnd ? 1u : 0u) | (uint32_t)(cnd ? pt.cond_coord : 0) << 1;
+                }
+                if constexpr (((T::PT_MOVING >> p) & 1u) != 0) {
+                    pw |= (pt.type == BIOIM_PT_MOVING ? 1u : 0u) << 6;
+#pragma unroll
+                    for (int a = 0; a < 3; ++a) {
+                        const int f = pt.mf[a];
+                        pw |= (f < 0 ? 32u : (uint32_t)f) << (8 + 6 * a);
+                    }
+                }
+                I.pt[j][p] = pw;
+            });
+            I.frame[j] = fw;
+        });
+    }
+}
+
 /* publish the coordinate values/speeds to LDS (QF/UF): dof lane d writes its
  * coordinate, lane 0 the locked coordinates (default value, zero speed) */
 template <class T, typename Real>
@@ -487,12 +604,14 @@ DEV void fn_slots(const SModel<T, Real> &SM, Real *lds, int lane) {
 }
 
 /* Phase 1c (lane = dof): ground Plucker column from the parent frame */
-template <class T, typename Real>
-DEV void kin_column(const SModel<T, Real> &SM, Real *lds, int d) {
+template <class T, typename Real, int LI = 0>
+DEV void kin_column(const SModel<T, Real> &SM, Real *lds, int d, const LaneIdx<T, Real> *I = nullptr) {
     using LY = Lay<T, Real>;
     using PL = Planar<T>;
     constexpr unsigned ZR = PL::ZR, ZW = PL::ZW, ZV = PL::ZV;
-    const Real *kp = lds + LY::KB + 18 * SM.body[SM.dof_cb[d]].pslot;
+    const Real *kp;
+    if constexpr ((LI & LI_COLS) != 0) kp = lds + I->kp();
+    else kp = lds + LY::KB + 18 * SM.body[SM.dof_cb[d]].pslot;
     const Real *sl = lds + LY::SL + 6 * d;
     Real K[12], sc[6];
 #pragma unroll

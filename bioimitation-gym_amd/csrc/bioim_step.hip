@@ -338,9 +338,9 @@ DEV Real muscle_equilibrium(const SModel<T, Real> &SM, const SMuscle<Real> &mu, 
  * coordinate.  The floating-base dofs are skipped: their sum over a path is
  * zero (sum g = 0, sum P x g = 0).  The span's Plucker columns are read from
  * LDS once per muscle into registers. */
-template <bool BFK, class T, typename Real>
+template <bool BFK, class T, typename Real, int LI = 0>
 DEV void muscle_path(const SModel<T, Real> &SM, const SMuscle<Real> &mu, const Real *lds, Real &L,
-                     Real (&dLs)[T::MAXSPAN]) {
+                     Real (&dLs)[T::MAXSPAN], const LaneIdx<T, Real> *I = nullptr, int jm = 0) {
     using LY = Lay<T, Real>;
     using PL = Planar<T>;
     constexpr unsigned ZR = PL::ZR, ZW = PL::ZW, ZV = PL::ZV;
@@ -357,7 +357,13 @@ DEV void muscle_path(const SModel<T, Real> &SM, const SMuscle<Real> &mu, const R
          * branch); the spatial kernels keep the branches (fewer live values
          * in their two muscle passes) */
         int dk;
-        if constexpr (BF) {
+        if constexpr ((LI & LI_PATH) != 0) {   /* the span's dof from the record (0 past nspan) */
+            const uint32_t w = I->path[jm];
+            const int spk = (int)li_bits(w, 16 + 4 * k, 4), none = -1;
+            const bool ink = k < (int)li_bits(w, 12, 4);
+            sd[k] = ink ? spk : none;
+            dk = spk;
+        } else if constexpr (BF) {
             const int spk = mu.span[k], none = -1, zero = 0;
             const bool ink = k < mu.nspan;
             sd[k] = ink ? spk : none;
@@ -387,7 +393,31 @@ DEV void muscle_path(const SModel<T, Real> &SM, const SMuscle<Real> &mu, const R
             dLs[k] += on * (sm + sg) + (mdofp == d && d >= 0 ? gd : Real(0));
         }
     };
-    const int npt = mu.npt;
+    /* the muscle's point count and first point (LI_PATH: from the record) */
+    auto path_npt = [&]() -> int {
+        if constexpr ((LI & LI_PATH) != 0) return (int)li_bits(I->path[jm], 8, 4);
+        else return mu.npt;
+    };
+    auto path_off = [&]() -> int {
+        if constexpr ((LI & LI_PATH) != 0) return (int)li_bits(I->path[jm], 0, 8);
+        else return mu.pt_off;
+    };
+    const int npt = path_npt();
+    /* point slot j's kind test and the function slot of its axis a, -1: the
+     * point's own location (LI_PATH: from the record) */
+    auto pt_is = [&](auto kI, const DPathPt<Real> &pt, int j) -> bool {
+        constexpr int kind = decltype(kI)::value;
+        if constexpr ((LI & LI_PATH) != 0) return ((I->pt[jm][j] >> (kind == BIOIM_PT_COND ? 0 : 6)) & 1u) != 0;
+        else return pt.type == kind;
+    };
+    auto pt_mf = [&](const DPathPt<Real> &pt, int j, int a) -> int {
+        if constexpr ((LI & LI_PATH) != 0) {
+            const uint32_t fw = li_bits(I->pt[jm][j], 8 + 6 * a, 6);
+            return (fw & 32u) ? -1 : (int)fw;
+        } else {
+            return pt.mf[a];
+        }
+    };
     constexpr int MP = T::MAXPT > 0 ? T::MAXPT : 1;
     /* every slot's body and activity first (branch-free, slot 0 for slots
      * past the count), so a point's frame loads wait on one LDS round trip
@@ -396,12 +426,16 @@ DEV void muscle_path(const SModel<T, Real> &SM, const SMuscle<Real> &mu, const R
     bool onj[MP];
     sfor<0, MP>([&](auto jI) {
         constexpr int j = decltype(jI)::value;
-        const DPathPt<Real> &pt = SM.pt[mu.pt_off + (j < npt ? j : 0)];
-        cbj[j] = pt.cbody;
+        const DPathPt<Real> &pt = SM.pt[path_off() + (j < npt ? j : 0)];
+        if constexpr ((LI & LI_PATH) != 0) cbj[j] = (int)li_bits(I->frame[jm], 4 * j, 4);
+        else cbj[j] = pt.cbody;
         onj[j] = j < npt;
         if constexpr (((T::PT_COND >> j) & 1u) != 0) {
-            const bool cnd = pt.type == BIOIM_PT_COND;
-            if constexpr (BF) {
+            const bool cnd = pt_is(std::integral_constant<int, BIOIM_PT_COND>{}, pt, j);
+            if constexpr ((LI & LI_PATH) != 0) {   /* the coordinate from the record (0: not conditional) */
+                const Real qc = ldsq[li_bits(I->pt[jm][j], 1, 5)], plo = pt.lo, phi = pt.hi;
+                onj[j] = onj[j] & !(cnd & ((qc < plo) | (qc > phi)));
+            } else if constexpr (BF) {
                 const int ccd = pt.cond_coord, zero = 0;
                 const Real qc = ldsq[cnd ? ccd : zero], plo = pt.lo, phi = pt.hi;
                 onj[j] = onj[j] & !(cnd & ((qc < plo) | (qc > phi)));   /* no short-circuit branches */
@@ -414,15 +448,15 @@ DEV void muscle_path(const SModel<T, Real> &SM, const SMuscle<Real> &mu, const R
     sfor<0, MP>([&](auto jI) {
         constexpr int j = decltype(jI)::value;
         {
-            const DPathPt<Real> &pt = SM.pt[mu.pt_off + j];
+            const DPathPt<Real> &pt = SM.pt[path_off() + j];
             if (onj[j]) {
                 Real loc[3] = {pt.loc[0], pt.loc[1], pt.loc[2]}, dloc[3] = {0, 0, 0};
                 if constexpr (((T::PT_MOVING >> j) & 1u) != 0) {
-                    if (pt.type == BIOIM_PT_MOVING) {
+                    if (pt_is(std::integral_constant<int, BIOIM_PT_MOVING>{}, pt, j)) {
                         Real ll[3], dl[3] = {0, 0, 0};
 #pragma unroll
                         for (int a = 0; a < 3; ++a) {
-                            const int f = pt.mf[a];
+                            const int f = pt_mf(pt, j, a);
                             if constexpr (BF) {
                                 const Real l0 = pt.loc[a], fv = lds[LY::MF + 3 * (f < 0 ? 0 : f)],
                                            fd = lds[LY::MF + 3 * (f < 0 ? 0 : f) + 1], zero = 0;
@@ -611,20 +645,27 @@ template <class T, bool IMP = true> struct BfSwitch {
 };
 
 /* The step-tail switch of one kernel family (BIOIM_GROUND_ONCE's bits) */
-template <class T, bool FUSED = false> struct TailSwitch {
+template <class T, bool FUSED = false, bool RK = false> struct TailSwitch {
     static constexpr int BIT = FUSED ? 4 : (T::PLANAR ? 1 : 2);
     static constexpr bool GROUND = (BIOIM_GROUND_ONCE & BIT) != 0;
     /* the family's BIOIM_FRONTEND byte (FE_* bits) */
     static constexpr int FE = (BIOIM_FRONTEND >> (FUSED ? 16 : (T::PLANAR ? 0 : 8))) & 0xFF;
+    /* the family's BIOIM_LANEIDX byte (LI_* bits); none in the RK kernels:
+     * LI_TAU put two flagged copies (tools/hazard_gate.py) into the Torque2D
+     * push + RK kernel, the one DESIGN.md 5.5 is about, so the reference
+     * integrator's kernels keep the parent's code */
+    static constexpr int LI = RK ? 0 : (BIOIM_LANEIDX >> (FUSED ? 16 : (T::PLANAR ? 0 : 8))) & 0xFF;
 };
 template <class T, typename Real, bool PERT, bool BF_ROWS, bool IMP, bool CACHE = false, class TS = TailSwitch<T>, bool EXT = false>
 DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Real ud,
                   const Real (&act)[Lay<T, Real>::MPL], const Real (&lce)[Lay<T, Real>::MPL],
                   const Real (&control)[Lay<T, Real>::MPL], int lane, Real *lds, Real h, bool equilibrate,
                   const PertArgs<Real> &P, double *pslot, int pk, Dyn<T, Real> &D, const CacheIO<T, Real> &CI,
-                  const ExtArgs<Real> &X = ExtArgs<Real>{}) {
+                  const LaneIdx<T, Real> &LXL, const ExtArgs<Real> &X = ExtArgs<Real>{}) {
     using LY = Lay<T, Real>;
     constexpr int ND = LY::ND, NP = LY::NP, NB = T::NB, G = T::G, MPL = LY::MPL;
+    constexpr int LI = TS::LI;   /* the family's BIOIM_LANEIDX byte: LX's fields in use */
+    const LaneIdx<T, Real> LX = LI != 0 ? LXL.template call_copy<LI>() : LXL;
     static_assert(!CACHE || (CacheLay<T>::ON && IMP && !PERT && !EXT), "the realize cache: the default (semi-implicit, no push, no external forces) step kernels");
     static_assert(NB < G && ND <= G, "lane NB writes the ground slot; one lane per dof");
     /* the semi-implicit planar kernels: the implicit contact / limit terms
@@ -635,6 +676,9 @@ DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Rea
      * every kernel (spatial too: no scratch; same-box 3D -1.6 %,
      * profiles/r03/r03k, r03l) */
     constexpr bool BFC = true;
+    /* LX's fields instead of the model image's tables (constant conditions:
+     * with a bit off the expression is the table read alone) */
+    constexpr bool LCOLS = (LI & LI_COLS) != 0, LTAU = (LI & LI_TAU) != 0;
     STAMP_DECL
     if (CACHE && CI.use) {
         /* the first substep of a launch from the last realize's cache: the
@@ -683,7 +727,7 @@ DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Rea
             if (lane < ND) {
                 Real r = lds[LY::RHS + lane];
 #pragma unroll
-                for (int i = 0; i < T::MAXARM; ++i) r += lds[LY::TAU + SM.tau_src[lane][i]];
+                for (int i = 0; i < T::MAXARM; ++i) r += lds[LY::TAU + (LTAU ? LX.tau_src(i) : SM.tau_src[lane][i])];
                 lds[LY::RHS + lane] = r;
             }
         }
@@ -744,7 +788,7 @@ DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Rea
         }
         wave_sync();
         STAMP(1);
-        if (lane < ND) kin_column<T, Real>(SM, lds, lane);
+        if (lane < ND) kin_column<T, Real, LI>(SM, lds, lane, &LX);
     } else {
         if (lane < NB) {
             Frame<Real> F;
@@ -752,7 +796,7 @@ DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Rea
         }
         wave_sync();
         STAMP(1);
-        if (lane < ND) kin_column<T, Real>(SM, lds, lane);
+        if (lane < ND) kin_column<T, Real, LI>(SM, lds, lane, &LX);
         if (lane < NB) {
             body_inertia<T, Real>(SM, M, lds, lane);
             push();
@@ -816,7 +860,7 @@ DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Rea
             if (m < T::NM) {
                 const SMuscle<Real> &mu = SM.mus[m];
                 Real L, dLs[T::MAXSPAN];
-                muscle_path<SW::PATH, T, Real>(SM, mu, lds, L, dLs);
+                muscle_path<SW::PATH, T, Real, LI>(SM, mu, lds, L, dLs, &LX, j);
                 STAMP(4);
                 Real a_ = act[j], l_ = lce[j];
                 if (equilibrate) /* equilibrateMuscles: static fiber equilibrium at the held activation
@@ -852,7 +896,7 @@ DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Rea
     }
     STAMP(6);
     if (lane < T::NL) {
-        int cc = SM.lim_coord[lane];
+        int cc = LTAU ? LX.lim_coord() : SM.lim_coord[lane];
         Real qv = lds[LY::QF + cc], qd = lds[LY::UF + cc];
         Real qup = SM.lim_qup[lane], qlo = SM.lim_qlow[lane], tr = SM.lim_trans[lane], itr = SM.lim_itrans[lane];
         Real up = smooth_step<SW::LIM>(Real(0), Real(1), qup, qup + tr, itr, qv);
@@ -900,18 +944,18 @@ DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Rea
 #pragma unroll
         for (int i = 0; i < 6; ++i) Sd[i] = lds[LY::S + 6 * lane + i];
         PL::col(Sd);
-        const Real *wb = lds + LY::WB + 6 * SM.dof_cb[lane];
+        const Real *wb = lds + LY::WB + 6 * (LCOLS ? LX.body() : SM.dof_cb[lane]);
         Real r = -(dot3m<ZW, 0>(Sd, wb) + dot3m<ZV, 0>(Sd + 3, wb + 3));
         /* torque models with the realize cache: the actuator torques last
          * (the cache keeps the sum before them) */
         constexpr bool TAU_LAST = CACHE && T::NM == 0;
         if constexpr (!TAU_LAST) {
 #pragma unroll
-            for (int i = 0; i < T::MAXARM; ++i) r += lds[LY::TAU + SM.tau_src[lane][i]];
+            for (int i = 0; i < T::MAXARM; ++i) r += lds[LY::TAU + (LTAU ? LX.tau_src(i) : SM.tau_src[lane][i])];
         }
         Real Gk[6];
         {
-            const Real *ic = lds + LY::IC + 10 * SM.dof_cb[lane];
+            const Real *ic = lds + LY::IC + 10 * (LCOLS ? LX.body() : SM.dof_cb[lane]);
             Real t[3];
             symvm<ZW>(ic + 4, Sd, Gk);
             cross3m<0, ZV>(ic + 1, Sd + 3, t);
@@ -962,14 +1006,14 @@ DEV void dynamics(const DModel<Real> &M, const SModel<T, Real> &SM, Real qd, Rea
         Real dg = 0;
 #pragma unroll
         for (int li = 0; li < T::NL; ++li) {   /* selects: no per-limit branch */
-            const bool mine = SM.lim_dof[li] == lane;
+            const bool mine = LTAU ? LX.lim_mine(li) : SM.lim_dof[li] == lane;
             r += mine ? lds[LY::LIM + 4 * li + (EX ? 0 : 2)] : Real(0);
             if constexpr (!EX) dg += mine ? lds[LY::LIM + 4 * li + 1] : Real(0);
         }
         if constexpr (TAU_LAST) {
             Real rt = r;
 #pragma unroll
-            for (int i = 0; i < T::MAXARM; ++i) rt += lds[LY::TAU + SM.tau_src[lane][i]];
+            for (int i = 0; i < T::MAXARM; ++i) rt += lds[LY::TAU + (LTAU ? LX.tau_src(i) : SM.tau_src[lane][i])];
             lds[LY::RHS + lane] = (!EX && CI.make) ? r : rt;   /* the cache's rhs: without the controls */
         } else {
             lds[LY::RHS + lane] = r;
@@ -3501,7 +3545,7 @@ template <class T, typename Real, bool PERT, bool RK, bool REP, bool FUSED = fal
 DEV void env_block(const LaunchArgs<T, Real> &a, int blk, const ExtArgs<Real> &xa = ExtArgs<Real>{}) {
     static_assert(!EXT || (!PERT && !RK && !FUSED), "external forces: the semi-implicit step and report kernels only");
     using LY = Lay<T, Real>;
-    using TS = TailSwitch<T, FUSED>;
+    using TS = TailSwitch<T, FUSED, RK>;
     constexpr int G = T::G, ND = LY::ND, NA = T::NA, NM = T::NM;
     constexpr int EPB = BIOIM_EPB;
     constexpr size_t SMB = smodel_bytes<T, Real>();
@@ -3555,6 +3599,10 @@ DEV void env_block(const LaunchArgs<T, Real> &a, int blk, const ExtArgs<Real> &x
             if constexpr (ground_loc_free<T, Real>()) kin_ground_loc<T, Real>(lds);
         }
     }
+    /* the lane's index record (BIOIM_LANEIDX), once per launch: it depends on
+     * the lane and the staged image alone */
+    LaneIdx<T, Real> LX{};
+    lane_index<TS::LI, T, Real>(SM, lane, LX);
     constexpr int MPL = LY::MPL;                  /* muscles / actions per lane: m = lane + j*G */
     constexpr int CPL = (T::NC + G - 1) / G;      /* coordinates per lane (report)              */
     Dyn<T, Real> D;
@@ -3919,7 +3967,7 @@ DEV void env_block(const LaunchArgs<T, Real> &a, int blk, const ExtArgs<Real> &x
              * (they would take those kernels past the 512-register budget) */
             dynamics<T, Real, PERT, !RK || T::PLANAR, !RK, CACHE, TS, EXT>(*(const DModel<Real> *)Mi, SM, qd, ud, act, lce, control, lane, lds,
                                     RK ? Real(0) : (sub ? dt : Real(0)), eq && NM > 0, PA, pslot,
-                                    RK ? 0 : M.nsub - remaining, D, CI, XE);
+                                    RK ? 0 : M.nsub - remaining, D, CI, LX, XE);
         }
         if (RK && sub) {
             const Real h = Real(rk_h);
