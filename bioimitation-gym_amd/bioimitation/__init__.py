@@ -7,10 +7,11 @@ UtkarshMishra04/bioimitation-gym), ``Env(config)`` classes with
 from .registry import REGISTERED_IDS, RECIPES, env_spec, load_pack  # noqa: F401
 
 __all__ = ['REGISTERED_IDS', 'RECIPES', 'env_spec', 'load_pack', 'VectorEnv', 'MixedVectorEnv', 'make',
-           'RLlibVectorEnv', 'GymVectorEnv', 'MeanStdFilter']
+           'RLlibVectorEnv', 'GymVectorEnv', 'MeanStdFilter', 'ComputedMuscleControl', 'CMCDrive']
 
 _LAZY = {'VectorEnv': 'vector_env', 'MixedVectorEnv': 'vector_env', 'make': 'envs', 'RLlibVectorEnv': 'adapters',
-         'GymVectorEnv': 'adapters', 'MeanStdFilter': 'adapters'}
+         'GymVectorEnv': 'adapters', 'MeanStdFilter': 'adapters', 'ComputedMuscleControl': 'computed_muscle_control',
+         'CMCDrive': 'computed_muscle_control'}
 
 
 def __getattr__(name):

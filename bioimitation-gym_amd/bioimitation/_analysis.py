@@ -68,6 +68,25 @@ def check_want(name, want, keys):
     return want
 
 
+def check_reserve(name, reserve, ndof):
+    """The row weights λ = 1/reserve² as a float64 array ``[ndof]``.
+    ``reserve``: a scalar or ``[ndof]`` of positive numbers, N·m, ``inf``
+    allowed (λ = 0 leaves the row out)."""
+    if hasattr(reserve, 'detach'):    # a torch tensor
+        reserve = reserve.detach().cpu().numpy()
+    try:
+        r = np.asarray(reserve, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f'{name}: reserve must hold real numbers') from None
+    if r.shape not in ((), (ndof,)):
+        raise ValueError(f'{name}: reserve must be a scalar or have shape ({ndof},), got {r.shape}')
+    if np.isnan(r).any() or (r < 0).any():
+        raise ValueError(f'{name}: reserve must be non-negative (inf allowed), not NaN')
+    if (r == 0).any():
+        raise ValueError(f'{name}: a reserve of 0 N·m has no finite weight; use a small positive value')
+    return np.broadcast_to(1.0 / (r * r), (ndof,)).copy()
+
+
 def to_device(x, device, dtype):
     """``x`` (None, array, tensor or nested list) as a contiguous tensor of
     ``dtype`` on ``device``."""

@@ -22,7 +22,7 @@ EXPORTS = ['bioim_create', 'bioim_destroy', 'bioim_reset', 'bioim_step', 'bioim_
            'bioim_finished_count', 'bioim_set_rk_counters', 'bioim_copy_state', 'bioim_copy_state_rows', 'bioim_load_state',
            'bioim_clone_envs', 'bioim_debug_plane', 'bioim_rollout', 'bioim_rollout_fused', 'bioim_rollout_group',
            'bioim_rollout_group_fused', 'bioim_muscle_eval', 'bioim_static_opt', 'bioim_ik_solve',
-           'bioim_joint_reaction', 'bioim_realize_report', 'bioim_induced_accel', 'bioim_body_kin']
+           'bioim_joint_reaction', 'bioim_realize_report', 'bioim_induced_accel', 'bioim_body_kin', 'bioim_cmc']
 
 _lib = None
 
@@ -57,6 +57,8 @@ def load():
         'bioim_id_eval': (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp]),
         'bioim_muscle_eval': (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         'bioim_static_opt': (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, vp, vp, vp, vp]),
+        'bioim_cmc': (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double,
+                                C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         'bioim_ik_solve': (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_int, vp, vp, vp, vp, vp]),
         'bioim_joint_reaction': (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
         'bioim_induced_accel': (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp]),

@@ -41,7 +41,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._analysis import Analysis, check_rows, check_want, ptr as p, to_device
+from ._analysis import Analysis, check_reserve, check_rows, check_want, ptr as p, to_device
 from .inverse_dynamics import RESIDUAL
 
 NAME = 'static optimization'
@@ -70,20 +70,7 @@ def check_args(ndof, nmuscle, q, u=None, qdd=None, tau=None, reserve=1.0, lo=0.0
         raise ValueError('static optimization: the bounds lo and hi must be numbers') from None
     if not (math.isfinite(lo) and math.isfinite(hi) and lo < hi):
         raise ValueError(f'static optimization: the bounds must be finite with lo < hi, got [{lo}, {hi}]')
-    if hasattr(reserve, 'detach'):    # a torch tensor
-        reserve = reserve.detach().cpu().numpy()
-    try:
-        r = np.asarray(reserve, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError('static optimization: reserve must hold real numbers') from None
-    if r.shape not in ((), (ndof,)):
-        raise ValueError(f'static optimization: reserve must be a scalar or have shape ({ndof},), got {r.shape}')
-    if np.isnan(r).any() or (r < 0).any():
-        raise ValueError('static optimization: reserve must be non-negative (inf allowed), not NaN')
-    if (r == 0).any():
-        raise ValueError('static optimization: a reserve of 0 N·m has no finite weight; use a small positive value')
-    lam = np.broadcast_to(1.0 / (r * r), (ndof,)).copy()
-    return n, want, lam
+    return n, want, check_reserve(NAME, reserve, ndof)
 
 
 def launch(env, q, u, tau, lam, lo, hi, passive, want):

@@ -606,6 +606,31 @@ class VectorEnv:
         _, want, lam = so.check_args(pk.ndof, pk.nmuscle, q, u, qdd, tau, reserve, lo, hi, want)
         return so.solve_on(self, q, u, qdd, tau, lam, lo, hi, passive, want)
 
+    def computed_muscle_control(self, qdd=None, tau=None, env_ids=None, q1=None, window=0.01, nsub=None, reserve=1.0,
+                                emin=0.0, emax=1.0, ftol=1e-6, max_iter=30, want=('excitation',), rows=None):
+        """Computed muscle control (``bioimitation.computed_muscle_control``)
+        at the envs' current q, u, activations and fiber lengths: the
+        excitations whose muscles deliver the target generalized force at the
+        end of ``window``, one row per env (or per listed env, in the list's
+        order).  Exactly one of ``qdd`` (accelerations; the target is then
+        their inverse-dynamics residual) and ``tau`` (the target itself),
+        ``[rows][ndof]``.  The state is gathered on the device
+        (``state_rows``) and goes to the launches on the env's stream: no host
+        round trip, no synchronization, and the envs are only read.  Muscle
+        envs in fp64 only (``ValueError`` otherwise).  ``rows``: state rows
+        already gathered for these envs, to spare the gather."""
+        from . import computed_muscle_control as cmc
+        from .packdef import state_row_slices
+        pk = self.pack
+        cmc.check_env(self)
+        if rows is None:
+            rows = self.state_rows(env_ids=env_ids)
+        sl, _ = state_row_slices(pk.ndof, pk.nmuscle, pk.nact, pk.horizon)
+        q, u, act, lce = (rows[:, sl[f]].contiguous() for f in ('q', 'u', 'act', 'lce'))
+        _, want, lam = cmc.check_args(pk.ndof, pk.nmuscle, q, u, act, lce, tau, qdd, q1, window, nsub, reserve,
+                                      emin, emax, ftol, max_iter, want)
+        return cmc.solve_on(self, q, u, act, lce, tau, qdd, q1, lam, window, nsub, emin, emax, ftol, max_iter, want)
+
     def _realize_report(self, ids, n):
         """The REALIZE report rows of the n listed envs (``ids``: a checked
         int32 device tensor) into ``self.osim_report``, on the env's stream.

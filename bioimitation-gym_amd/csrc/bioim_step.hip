@@ -1534,7 +1534,10 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_e
  * workgroup barrier follows the idx >= n exit.  No atomics, no read-modify-
  * write at run-time indices shared between lanes, sums in a fixed order: a
  * state's result does not depend on n or its neighbours.  Matrices, sets and
- * flags live in LDS; the per-lane arrays have compile-time indices only. */
+ * flags live in LDS; the per-lane arrays have compile-time indices only.
+ * The iteration itself is box_qp_solve, with a lower and an upper bound per
+ * variable in LDS (SoLay::LO / HI), shared with cmc_kernel; this kernel writes
+ * its two scalars there. */
 
 template <typename P> struct SoFields {   /* bioim_static_opt (fp64 only) */
     int n, passive;
@@ -1561,10 +1564,13 @@ template <class T, typename Real> struct SoLay {
     static constexpr int END = RER + ND;
     static constexpr int BS = LY::TAU;         /* [MPL G][NSP] + zero slot: B entries by lane slot        */
     static constexpr int CS = BS + LY::TAUN;   /* the same for -dL/dq Fp                                  */
+    static constexpr int LO = CS;              /* the solve: [NM] lower bounds by slot (the passive entries */
+    static constexpr int HI = LO + NM;         /* are summed by then), [NM] upper bounds                  */
     static constexpr int CAP = 8 * NM;         /* passes; the most observed: 21 (NM = 14), 29 (NM = 22), 18 (NM = 19) */
     static_assert(END <= LY::U, "the solver's data must fit below the union region");
     static_assert(NM * NSP <= NH + NM, "the dof table must fit in the work matrix");
     static_assert(CS + LY::TAUN <= LY::SIZE0, "two slot arrays must fit in the union region");
+    static_assert(2 * NM <= LY::TAUN, "the bounds must fit in the second slot array");
 };
 
 /* Rigid-tendon capacity of one muscle at path length L and lengthening speed
@@ -1595,6 +1601,254 @@ DEV void muscle_rigid_capacity(const SModel<T, Real> &SM, const SMuscle<Real> &m
     const Real zero_f = 0;
     Fa = Fa > zero_f ? Fa : zero_f;
     Fp = Fp > zero_f ? Fp : zero_f;
+}
+
+/* The box QP's solve (the comment above: passes, ties, caps, status codes),
+ * shared by so_kernel and cmc_kernel:
+ *     min sum_s x_s^2 + sum_d lam_d (tc_d - (B x)_d)^2,  LO_s <= x_s <= HI_s.
+ * On entry the state's LDS region holds the B entries by lane slot (SoLay::BS,
+ * with its zero slot) and every lane has written the bounds of its own slots
+ * to SoLay::LO / HI, in the second slot array (so_kernel: its two scalars,
+ * broadcast, once the passive entries there are summed); mi[j] is the
+ * slot's muscle (NM: none), lam and tc the dof lane's row weight and target.
+ * A variable whose range is empty (HI <= LO) stays bound at LO and is never
+ * offered to the iteration.  On return xv[j] (and SoLay::X by slot) hold the
+ * solution; the value is the state's status.  Every lane of the state calls
+ * it; [0, Lay::U) must be dead (it becomes the solver's, SoLay). */
+template <class T, typename Real>
+DEV int box_qp_solve(const SModel<T, Real> &SM, Real *lds, int lane, const int (&mi)[Lay<T, Real>::MPL], Real lam,
+                     Real tc, Real (&xv)[Lay<T, Real>::MPL]) {
+    using LY = Lay<T, Real>;
+    using SL = SoLay<T, Real>;
+    constexpr int G = T::G, ND = LY::ND, NM = T::NM, MPL = LY::MPL, NSP = T::MAXSPAN, NH = SL::NH;
+    /* muscle lanes: the slot's bounds; the variables start at lo; the dof table
+     * of the B entries; own entries and dofs to registers */
+    Real lo[MPL], hi[MPL], fl[MPL], bown[MPL][NSP];
+    int down[MPL][NSP];
+    bool blk[MPL], fixed[MPL];
+    sfor<0, MPL>([&](auto jI) {
+        constexpr int j = decltype(jI)::value;
+        const int s = lane + j * G;
+        lo[j] = s < NM ? lds[SL::LO + s] : Real(0);
+        hi[j] = s < NM ? lds[SL::HI + s] : Real(0);
+        fixed[j] = !(hi[j] > lo[j]);   /* an empty range: bound at lo for good */
+        xv[j] = lo[j]; fl[j] = Real(-1); blk[j] = false;
+        const SMuscle<Real> &mu = SM.mus[mi[j] < NM ? mi[j] : 0];
+#pragma unroll
+        for (int k = 0; k < NSP; ++k) {
+            const bool in = mi[j] < NM && k < mu.nspan;
+            down[j][k] = in ? mu.span[k] : -1;
+            bown[j][k] = lds[SL::BS + s * NSP + k];
+            if (s < NM) lds[SL::DSP + s * NSP + k] = Real(down[j][k]);
+        }
+        if (s < NM) { lds[SL::X + s] = lo[j]; lds[SL::F + s] = Real(-1); }
+    });
+    if (lane < ND) lds[SL::RHO + lane] = lam;   /* lam_d, for the assembly (RHO is rewritten per pass) */
+    wave_sync();
+    /* H: row s (uniform), the lane's columns t <= s */
+    for (int s = 0; s < NM; ++s) {
+        Real ws[NSP], dsr[NSP];
+#pragma unroll
+        for (int k = 0; k < NSP; ++k) {
+            dsr[k] = lds[SL::DSP + s * NSP + k];
+            const int dk = dsr[k] >= Real(0) ? (int)dsr[k] : 0;
+            ws[k] = lds[SL::RHO + dk] * lds[SL::BS + s * NSP + k];   /* lam_d B_ds (0 for an unused entry) */
+        }
+        sfor<0, MPL>([&](auto jI) {
+            constexpr int j = decltype(jI)::value;
+            const int t = lane + j * G;
+            if (t <= s) {
+                Real acc = t == s ? Real(1) : Real(0);
+#pragma unroll
+                for (int k = 0; k < NSP; ++k)
+#pragma unroll
+                    for (int kk = 0; kk < NSP; ++kk)
+                        acc += (dsr[k] == Real(down[j][kk]) && down[j][kk] >= 0) ? ws[k] * bown[j][kk] : Real(0);
+                lds[SL::H + s * (s + 1) / 2 + t] = acc;
+            }
+        });
+    }
+    wave_sync();   /* the dof table is dead: its place is the work matrix */
+    const Real tiny = Real(16) * Real(2.220446049250313e-16);   /* 16 ulp of the sums that form w */
+    int status = 0, it = 0, mode = 0, tnew = -1;
+    bool done = false;
+    while (!done) {
+        /* rho and its rounding scale (dof lanes), then w (muscle lanes) */
+        if (lane < ND) {
+            Real sum = 0, asum = 0;
+#pragma unroll
+            for (int i = 0; i < T::MAXARM; ++i) {
+                const int src = SM.tau_src[lane][i];
+                const int sx = src / NSP < NM ? src / NSP : NM - 1;
+                const Real term = lds[SL::BS + src] * lds[SL::X + sx];   /* the zero slot: B = 0 */
+                sum += term; asum += fabs(term);
+            }
+            lds[SL::RHO + lane] = lam * (tc - sum);
+            lds[SL::RER + lane] = lam * (fabs(tc) + asum);
+        }
+        wave_sync();
+        Real wv[MPL], wtol[MPL];
+        sfor<0, MPL>([&](auto jI) {
+            constexpr int j = decltype(jI)::value;
+            Real w = 0, e = 0;
+#pragma unroll
+            for (int k = 0; k < NSP; ++k) {
+                const int dk = down[j][k] >= 0 ? down[j][k] : 0;
+                w += bown[j][k] * lds[SL::RHO + dk];
+                e += fabs(bown[j][k]) * lds[SL::RER + dk];
+            }
+            wv[j] = w - xv[j];
+            wtol[j] = tiny * (e + fabs(xv[j]));
+        });
+        if (mode == 0) {
+            /* CHECK: free the bound variable whose w points furthest inward */
+            Real best = 0;
+            Real sc[MPL];
+            int bad = 0;
+            sfor<0, MPL>([&](auto jI) {
+                constexpr int j = decltype(jI)::value;
+                bad |= (mi[j] < NM && !(wv[j] == wv[j])) ? 1 : 0;   /* a NaN came in */
+                Real v = fl[j] < Real(0) ? wv[j] : (fl[j] > Real(0) ? -wv[j] : Real(0));
+                v = (mi[j] < NM && !blk[j] && !fixed[j] && v > wtol[j]) ? v : Real(0);
+                sc[j] = v;
+                best = v > best ? v : best;
+            });
+            best = group_max<G>(best);
+            if (group_min<G>(-bad) < 0) {
+                done = true;
+                status = -2;
+            } else if (!(best > Real(0))) {
+                done = true;
+                status = it;
+            } else {
+                int cand = NM;
+                sfor<0, MPL>([&](auto jI) {
+                    constexpr int j = decltype(jI)::value;
+                    cand = (sc[j] == best && mi[j] < cand) ? mi[j] : cand;
+                });
+                const int t = group_min<G>(cand);
+                sfor<0, MPL>([&](auto jI) {
+                    constexpr int j = decltype(jI)::value;
+                    if (mi[j] == t) { fl[j] = Real(0); lds[SL::F + lane + j * G] = Real(0); }
+                });
+                tnew = t;
+                mode = 1;
+            }
+        }
+        if (!done && ++it > SL::CAP) {
+            done = true;
+            status = -1;
+        }
+        if (!done) {
+            wave_sync();
+            /* the masked matrix (bound rows and columns: identity) and, as row NM, the right-hand side */
+            for (int i = 0; i < NM; ++i) {
+                const bool fi = lds[SL::F + i] == Real(0);
+                sfor<0, MPL>([&](auto jI) {
+                    constexpr int j = decltype(jI)::value;
+                    const int t = lane + j * G;
+                    if (t <= i) {
+                        const int e = i * (i + 1) / 2 + t;
+                        const Real hv = lds[SL::H + e];
+                        lds[SL::A + e] = (fi && fl[j] == Real(0)) ? hv : (t == i ? Real(1) : Real(0));
+                    }
+                });
+            }
+            sfor<0, MPL>([&](auto jI) {
+                constexpr int j = decltype(jI)::value;
+                const int t = lane + j * G;
+                if (t < NM) lds[SL::A + NH + t] = fl[j] == Real(0) ? wv[j] : Real(0);
+            });
+            wave_sync();
+            /* Cholesky, right-looking; row NM comes out as L^-1 rhs */
+            bool ok = true;
+            for (int k = 0; k < NM && ok; ++k) {
+                const Real piv = lds[SL::A + k * (k + 1) / 2 + k];
+                ok = piv > Real(0);
+                if (ok) {
+                    const Real rp = Real(1) / sqrt(piv);
+                    for (int i = k + 1 + lane; i <= NM; i += G) lds[SL::A + i * (i + 1) / 2 + k] *= rp;
+                    if (lane == 0) lds[SL::D + k] = rp;
+                    wave_sync();
+                    for (int i = k + 1 + lane; i <= NM; i += G) {
+                        Real *ri = lds + SL::A + i * (i + 1) / 2;
+                        const Real lik = ri[k];
+                        const int je = i < NM ? i : NM - 1;
+                        for (int jc = k + 1; jc <= je; ++jc) ri[jc] -= lik * lds[SL::A + jc * (jc + 1) / 2 + k];
+                    }
+                    wave_sync();
+                }
+            }
+            if (!ok) {
+                done = true;
+                status = -2;
+            } else {
+                /* L^T dz = y, last row first */
+                for (int k = NM - 1; k >= 0; --k) {
+                    const Real zk = lds[SL::A + NH + k] * lds[SL::D + k];
+                    const Real *rk = lds + SL::A + k * (k + 1) / 2;
+                    for (int i = lane; i < k; i += G) lds[SL::A + NH + i] -= rk[i] * zk;
+                    if (lane == 0) lds[SL::Z + k] = zk;
+                    wave_sync();
+                }
+                /* the step: whole if it stays in the box, else to the first bound met */
+                Real zv[MPL], al[MPL], bd[MPL];
+                Real amin = Real(2);
+                sfor<0, MPL>([&](auto jI) {
+                    constexpr int j = decltype(jI)::value;
+                    const int t = lane + j * G;
+                    const bool fr = t < NM && fl[j] == Real(0);
+                    zv[j] = fr ? xv[j] + lds[SL::Z + (t < NM ? t : 0)] : xv[j];
+                    const bool under = fr && zv[j] < lo[j], over = fr && zv[j] > hi[j];
+                    bd[j] = under ? lo[j] : hi[j];
+                    const Real den = zv[j] - xv[j];
+                    Real av = (under || over) ? (bd[j] - xv[j]) / den : Real(2);
+                    av = av < Real(0) ? Real(0) : av;     /* an under / over step has den != 0; rounding only */
+                    al[j] = (under || over) ? (av < Real(1) ? av : Real(1)) : Real(2);
+                    amin = al[j] < amin ? al[j] : amin;
+                });
+                amin = group_min<G>(amin);
+                if (amin > Real(1)) {   /* inside the box: take it, check again */
+                    sfor<0, MPL>([&](auto jI) {
+                        constexpr int j = decltype(jI)::value;
+                        xv[j] = zv[j];
+                        blk[j] = false;
+                    });
+                    mode = 0;
+                } else {
+                    int cand = NM;
+                    sfor<0, MPL>([&](auto jI) {
+                        constexpr int j = decltype(jI)::value;
+                        cand = (al[j] == amin && mi[j] < cand) ? mi[j] : cand;
+                    });
+                    const int jm = group_min<G>(cand);
+                    const bool back = jm == tnew && amin == Real(0);   /* freed by rounding noise */
+                    sfor<0, MPL>([&](auto jI) {
+                        constexpr int j = decltype(jI)::value;
+                        const int t = lane + j * G;
+                        if (t < NM && fl[j] == Real(0)) xv[j] = xv[j] + amin * (zv[j] - xv[j]);
+                        if (mi[j] == jm) {
+                            xv[j] = bd[j];
+                            fl[j] = bd[j] == lo[j] ? Real(-1) : Real(1);
+                            blk[j] = back;
+                            lds[SL::F + t] = fl[j];
+                        }
+                        /* a free variable the partial step leaves outside by rounding stays inside */
+                        xv[j] = xv[j] < lo[j] ? lo[j] : (xv[j] > hi[j] ? hi[j] : xv[j]);
+                    });
+                    if (back) mode = 0;
+                }
+                tnew = -1;
+                sfor<0, MPL>([&](auto jI) {
+                    constexpr int j = decltype(jI)::value;
+                    const int t = lane + j * G;
+                    if (t < NM) lds[SL::X + t] = xv[j];
+                });
+            }
+        }
+        wave_sync();
+    }
+    return status;
 }
 
 template <class T, typename Real>
@@ -1689,230 +1943,15 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_e
         for (int i = 0; i < T::MAXARM; ++i) cq += lds[SL::CS + SM.tau_src[lane][i]];
         tc = tq - cq;
     }
-    /* muscle lanes: the variables start at lo; the dof table of the B entries;
-     * own entries and dofs to registers */
-    Real xv[MPL], fl[MPL], bown[MPL][NSP];
-    int down[MPL][NSP];
-    bool blk[MPL];
+    wave_sync();   /* the passive entries are summed: their place takes the bounds */
+    /* the bounds of the lane's own slots, then the solve */
+    Real xv[MPL];
     sfor<0, MPL>([&](auto jI) {
         constexpr int j = decltype(jI)::value;
         const int s = lane + j * G;
-        xv[j] = lo; fl[j] = Real(-1); blk[j] = false;
-        const SMuscle<Real> &mu = SM.mus[mi[j] < NM ? mi[j] : 0];
-#pragma unroll
-        for (int k = 0; k < NSP; ++k) {
-            const bool in = mi[j] < NM && k < mu.nspan;
-            down[j][k] = in ? mu.span[k] : -1;
-            bown[j][k] = lds[SL::BS + s * NSP + k];
-            if (s < NM) lds[SL::DSP + s * NSP + k] = Real(down[j][k]);
-        }
-        if (s < NM) { lds[SL::X + s] = lo; lds[SL::F + s] = Real(-1); }
+        if (s < NM) { lds[SL::LO + s] = lo; lds[SL::HI + s] = hi; }
     });
-    if (lane < ND) lds[SL::RHO + lane] = lam;   /* lam_d, for the assembly (RHO is rewritten per pass) */
-    wave_sync();
-    /* H: row s (uniform), the lane's columns t <= s */
-    for (int s = 0; s < NM; ++s) {
-        Real ws[NSP], dsr[NSP];
-#pragma unroll
-        for (int k = 0; k < NSP; ++k) {
-            dsr[k] = lds[SL::DSP + s * NSP + k];
-            const int dk = dsr[k] >= Real(0) ? (int)dsr[k] : 0;
-            ws[k] = lds[SL::RHO + dk] * lds[SL::BS + s * NSP + k];   /* lam_d B_ds (0 for an unused entry) */
-        }
-        sfor<0, MPL>([&](auto jI) {
-            constexpr int j = decltype(jI)::value;
-            const int t = lane + j * G;
-            if (t <= s) {
-                Real acc = t == s ? Real(1) : Real(0);
-#pragma unroll
-                for (int k = 0; k < NSP; ++k)
-#pragma unroll
-                    for (int kk = 0; kk < NSP; ++kk)
-                        acc += (dsr[k] == Real(down[j][kk]) && down[j][kk] >= 0) ? ws[k] * bown[j][kk] : Real(0);
-                lds[SL::H + s * (s + 1) / 2 + t] = acc;
-            }
-        });
-    }
-    wave_sync();   /* the dof table is dead: its place is the work matrix */
-    const Real tiny = Real(16) * Real(2.220446049250313e-16);   /* 16 ulp of the sums that form w */
-    int status = 0, it = 0, mode = 0, tnew = -1;
-    bool done = false;
-    while (!done) {
-        /* rho and its rounding scale (dof lanes), then w (muscle lanes) */
-        if (lane < ND) {
-            Real sum = 0, asum = 0;
-#pragma unroll
-            for (int i = 0; i < T::MAXARM; ++i) {
-                const int src = SM.tau_src[lane][i];
-                const int sx = src / NSP < NM ? src / NSP : NM - 1;
-                const Real term = lds[SL::BS + src] * lds[SL::X + sx];   /* the zero slot: B = 0 */
-                sum += term; asum += fabs(term);
-            }
-            lds[SL::RHO + lane] = lam * (tc - sum);
-            lds[SL::RER + lane] = lam * (fabs(tc) + asum);
-        }
-        wave_sync();
-        Real wv[MPL], wtol[MPL];
-        sfor<0, MPL>([&](auto jI) {
-            constexpr int j = decltype(jI)::value;
-            Real w = 0, e = 0;
-#pragma unroll
-            for (int k = 0; k < NSP; ++k) {
-                const int dk = down[j][k] >= 0 ? down[j][k] : 0;
-                w += bown[j][k] * lds[SL::RHO + dk];
-                e += fabs(bown[j][k]) * lds[SL::RER + dk];
-            }
-            wv[j] = w - xv[j];
-            wtol[j] = tiny * (e + fabs(xv[j]));
-        });
-        if (mode == 0) {
-            /* CHECK: free the bound variable whose w points furthest inward */
-            Real best = 0;
-            Real sc[MPL];
-            int bad = 0;
-            sfor<0, MPL>([&](auto jI) {
-                constexpr int j = decltype(jI)::value;
-                bad |= (mi[j] < NM && !(wv[j] == wv[j])) ? 1 : 0;   /* a NaN came in */
-                Real v = fl[j] < Real(0) ? wv[j] : (fl[j] > Real(0) ? -wv[j] : Real(0));
-                v = (mi[j] < NM && !blk[j] && v > wtol[j]) ? v : Real(0);
-                sc[j] = v;
-                best = v > best ? v : best;
-            });
-            best = group_max<G>(best);
-            if (group_min<G>(-bad) < 0) {
-                done = true;
-                status = -2;
-            } else if (!(best > Real(0))) {
-                done = true;
-                status = it;
-            } else {
-                int cand = NM;
-                sfor<0, MPL>([&](auto jI) {
-                    constexpr int j = decltype(jI)::value;
-                    cand = (sc[j] == best && mi[j] < cand) ? mi[j] : cand;
-                });
-                const int t = group_min<G>(cand);
-                sfor<0, MPL>([&](auto jI) {
-                    constexpr int j = decltype(jI)::value;
-                    if (mi[j] == t) { fl[j] = Real(0); lds[SL::F + lane + j * G] = Real(0); }
-                });
-                tnew = t;
-                mode = 1;
-            }
-        }
-        if (!done && ++it > SL::CAP) {
-            done = true;
-            status = -1;
-        }
-        if (!done) {
-            wave_sync();
-            /* the masked matrix (bound rows and columns: identity) and, as row NM, the right-hand side */
-            for (int i = 0; i < NM; ++i) {
-                const bool fi = lds[SL::F + i] == Real(0);
-                sfor<0, MPL>([&](auto jI) {
-                    constexpr int j = decltype(jI)::value;
-                    const int t = lane + j * G;
-                    if (t <= i) {
-                        const int e = i * (i + 1) / 2 + t;
-                        const Real hv = lds[SL::H + e];
-                        lds[SL::A + e] = (fi && fl[j] == Real(0)) ? hv : (t == i ? Real(1) : Real(0));
-                    }
-                });
-            }
-            sfor<0, MPL>([&](auto jI) {
-                constexpr int j = decltype(jI)::value;
-                const int t = lane + j * G;
-                if (t < NM) lds[SL::A + NH + t] = fl[j] == Real(0) ? wv[j] : Real(0);
-            });
-            wave_sync();
-            /* Cholesky, right-looking; row NM comes out as L^-1 rhs */
-            bool ok = true;
-            for (int k = 0; k < NM && ok; ++k) {
-                const Real piv = lds[SL::A + k * (k + 1) / 2 + k];
-                ok = piv > Real(0);
-                if (ok) {
-                    const Real rp = Real(1) / sqrt(piv);
-                    for (int i = k + 1 + lane; i <= NM; i += G) lds[SL::A + i * (i + 1) / 2 + k] *= rp;
-                    if (lane == 0) lds[SL::D + k] = rp;
-                    wave_sync();
-                    for (int i = k + 1 + lane; i <= NM; i += G) {
-                        Real *ri = lds + SL::A + i * (i + 1) / 2;
-                        const Real lik = ri[k];
-                        const int je = i < NM ? i : NM - 1;
-                        for (int jc = k + 1; jc <= je; ++jc) ri[jc] -= lik * lds[SL::A + jc * (jc + 1) / 2 + k];
-                    }
-                    wave_sync();
-                }
-            }
-            if (!ok) {
-                done = true;
-                status = -2;
-            } else {
-                /* L^T dz = y, last row first */
-                for (int k = NM - 1; k >= 0; --k) {
-                    const Real zk = lds[SL::A + NH + k] * lds[SL::D + k];
-                    const Real *rk = lds + SL::A + k * (k + 1) / 2;
-                    for (int i = lane; i < k; i += G) lds[SL::A + NH + i] -= rk[i] * zk;
-                    if (lane == 0) lds[SL::Z + k] = zk;
-                    wave_sync();
-                }
-                /* the step: whole if it stays in the box, else to the first bound met */
-                Real zv[MPL], al[MPL], bd[MPL];
-                Real amin = Real(2);
-                sfor<0, MPL>([&](auto jI) {
-                    constexpr int j = decltype(jI)::value;
-                    const int t = lane + j * G;
-                    const bool fr = t < NM && fl[j] == Real(0);
-                    zv[j] = fr ? xv[j] + lds[SL::Z + (t < NM ? t : 0)] : xv[j];
-                    const bool under = fr && zv[j] < lo, over = fr && zv[j] > hi;
-                    bd[j] = under ? lo : hi;
-                    const Real den = zv[j] - xv[j];
-                    Real av = (under || over) ? (bd[j] - xv[j]) / den : Real(2);
-                    av = av < Real(0) ? Real(0) : av;     /* an under / over step has den != 0; rounding only */
-                    al[j] = (under || over) ? (av < Real(1) ? av : Real(1)) : Real(2);
-                    amin = al[j] < amin ? al[j] : amin;
-                });
-                amin = group_min<G>(amin);
-                if (amin > Real(1)) {   /* inside the box: take it, check again */
-                    sfor<0, MPL>([&](auto jI) {
-                        constexpr int j = decltype(jI)::value;
-                        xv[j] = zv[j];
-                        blk[j] = false;
-                    });
-                    mode = 0;
-                } else {
-                    int cand = NM;
-                    sfor<0, MPL>([&](auto jI) {
-                        constexpr int j = decltype(jI)::value;
-                        cand = (al[j] == amin && mi[j] < cand) ? mi[j] : cand;
-                    });
-                    const int jm = group_min<G>(cand);
-                    const bool back = jm == tnew && amin == Real(0);   /* freed by rounding noise */
-                    sfor<0, MPL>([&](auto jI) {
-                        constexpr int j = decltype(jI)::value;
-                        const int t = lane + j * G;
-                        if (t < NM && fl[j] == Real(0)) xv[j] = xv[j] + amin * (zv[j] - xv[j]);
-                        if (mi[j] == jm) {
-                            xv[j] = bd[j];
-                            fl[j] = bd[j] == lo ? Real(-1) : Real(1);
-                            blk[j] = back;
-                            lds[SL::F + t] = fl[j];
-                        }
-                        /* a free variable the partial step leaves outside by rounding stays inside */
-                        xv[j] = xv[j] < lo ? lo : (xv[j] > hi ? hi : xv[j]);
-                    });
-                    if (back) mode = 0;
-                }
-                tnew = -1;
-                sfor<0, MPL>([&](auto jI) {
-                    constexpr int j = decltype(jI)::value;
-                    const int t = lane + j * G;
-                    if (t < NM) lds[SL::X + t] = xv[j];
-                });
-            }
-        }
-        wave_sync();
-    }
+    const int status = box_qp_solve<T, Real>(SM, lds, lane, mi, lam, tc, xv);
     /* outputs: act by muscle; tau_muscle = B a + c, residual = tau - tau_muscle by dof */
     sfor<0, MPL>([&](auto jI) {
         constexpr int j = decltype(jI)::value;
@@ -1930,6 +1969,261 @@ __global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_e
         const Real tm = sum + cq;
         if (a.tau_muscle) GAT(a.tau_muscle, (size_t)idx * ND + lane, (size_t)a.n * ND) = tm;
         if (a.residual) GAT(a.residual, (size_t)idx * ND + lane, (size_t)a.n * ND) = tq - tm;
+    }
+}
+
+/* ------------------------------------------------- computed muscle control
+ * bioim_cmc (include/bioim.h): per state the excitations whose muscles, run
+ * through the step's own activation and contraction dynamics over a window T,
+ * deliver at its end the forces that produce a target generalized force.
+ * fp64 only.
+ *
+ * so_kernel's launch shape and prologue, the kinematics run twice: at q for
+ * the path lengths L0, then (after a wave_sync: every lane has read the first
+ * frames) at q1 for L1 and dL/dq, with so_kernel's structural zeros.  Lane l
+ * owns the muscles of slots l, l + G through all four phases.
+ *   2. cmc_predict at the two ends of the slot's excitation bracket: registers
+ *      only (the muscle substep reads the model image, nothing of the state's
+ *      LDS region), so the lanes of a wave need no order among them.
+ *   3. B = -dL/dq F0 by slot in the step's TAU slots (SoLay::BS), the force
+ *      range over F0 as the slot's bounds (SoLay::LO / HI), box_qp_solve.
+ *   4. Illinois on P(e) - F* per slot, each lane under its own count, at most
+ *      max_iter evaluations; no LDS traffic, no barrier inside.
+ * LDS: Lay's state region as so_kernel uses it (SoLay below Lay::U, the slot
+ * array at Lay::TAU, the bounds in the second slot array, which has no passive
+ * entries to hold here); nothing is added.  Loops: nsub + 1 muscle evaluations
+ * per predictor, 2 + max_iter predictors per slot, SoLay::CAP passes, and
+ * solve_fv's own cap inside muscle_eval.  No atomics, fixed summation order: a
+ * state's result does not depend on n or its neighbours. */
+template <typename P> struct CmcFields {   /* bioim_cmc (fp64 only) */
+    int n, nsub, max_iter;
+    const P *q, *u, *act, *lce, *q1, *tau, *row_weight;
+    double window, emin, emax, ftol;
+    P *excitation, *force, *force_range, *predicted, *state_end, *tau_muscle, *residual;
+    int32_t *status, *root_status;
+};
+
+/* a b + c in two roundings whatever the contraction mode: q + T u must equal
+ * the caller's own product and sum bit for bit */
+template <typename Real> DEV Real mul_then_add(Real a, Real b, Real c) {
+    Real p = a * b;
+    asm volatile("" : "+v"(p));
+    return p + c;
+}
+
+/* The predictor P_m(e): from (a0, l0) nsub muscle substeps of length h at
+ * constant excitation e, substep k at path length L0 + (k / nsub)(L1 - L0) with
+ * a cold fiber-velocity start, the updates those of the step (a += h da/dt;
+ * unless clamped l += h vce / (1 - h dvce/dl), cut at l_min); then one more
+ * evaluation at the end state and L1, whose tendon force is the value.  aE, lE:
+ * the end state. */
+template <class T, typename Real>
+DEV Real cmc_predict(const SModel<T, Real> &SM, const SMuscle<Real> &mu, Real a0, Real l0, Real L0, Real L1, Real e,
+                     Real h, int nsub, Real &aE, Real &lE) {
+    using SW = BfSwitch<T>;
+    Real av = a0, lv = l0, Ft = 0;
+    const Real dL = L1 - L0, rn = Real(nsub);
+#pragma nounroll
+    for (int k = 0; k <= nsub; ++k) {
+        const Real L = k < nsub ? L0 + (Real(k) / rn) * dL : L1;
+        MState<Real> ms;
+        muscle_eval<SW::ME, true, T, Real>(SM, mu, av, lv, e, L, Real(0), ms);
+        Ft = ms.Ft;
+        if (k < nsub) {
+            av += h * ms.dadt;
+            if (!ms.clamped) {
+#if BIOIM_SUBSTEP_RCP
+                const Real ln = lv + h * ms.vce * fast_rcp(Real(1) - h * ms.dvdl);
+#else
+                const Real ln = lv + h * ms.vce / (Real(1) - h * ms.dvdl);
+#endif
+                lv = ln < mu.lmin ? mu.lmin : ln;
+            }
+        }
+    }
+    aE = av;
+    lE = lv;
+    return Ft;
+}
+
+template <class T, typename Real>
+__global__ __launch_bounds__(BIOIM_EPB * T::G) __attribute__((amdgpu_waves_per_eu(1, 1))) void cmc_kernel(ModelArgs<T, Real> md, CmcFields<Real> a) {
+    using LY = Lay<T, Real>;
+    using SL = SoLay<T, Real>;
+    using SW = BfSwitch<T>;
+    constexpr int G = T::G, ND = LY::ND, NM = T::NM, MPL = LY::MPL, NSP = T::MAXSPAN, EPB = BIOIM_EPB;
+    constexpr size_t SMB = smodel_bytes<T, Real>();
+    static_assert(NM > 0, "muscle topologies only");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const SModel<T, Real> &SM = stage_model<EPB, T, Real>(md.Sg, smem_raw);
+    const DModel<Real> &M = *md.Mg;
+    const int lane = threadIdx.x % G, slot = threadIdx.x / G;
+    const int idx = blockIdx.x * EPB + slot;
+    if (idx >= a.n) return;
+    Real *lds = reinterpret_cast<Real *>(smem_raw + SMB) + slot * LY::SIZE;
+    const size_t rows = (size_t)a.n * NM;
+    Real qd = 0, ud = 0, q1d = 0;
+    if (lane < ND) {
+        qd = GAT(a.q, (size_t)idx * ND + lane, (size_t)a.n * ND);
+        ud = GAT(a.u, (size_t)idx * ND + lane, (size_t)a.n * ND);
+        q1d = a.q1 ? GAT(a.q1, (size_t)idx * ND + lane, (size_t)a.n * ND) : mul_then_add<Real>(a.window, ud, qd);
+    }
+    /* phase 1: L0 at q, then L1 and dL/dq at q1 */
+    state_kinematics<SW::FN, T, Real>(M, SM, lds, lane, qd, ud);
+    wave_sync();
+    int mi[MPL];     /* the slot's muscle (NM: none) */
+    Real L0[MPL], L1[MPL];
+    sfor<0, MPL>([&](auto jI) {
+        constexpr int j = decltype(jI)::value;
+        const int m = mslot<T>(lane + j * G);
+        mi[j] = m < NM ? m : NM;
+        L0[j] = 0;
+        if (m < NM) {
+            Real dLs[NSP];
+            muscle_path<SW::PATH, T, Real>(SM, SM.mus[m], lds, L0[j], dLs);
+        }
+    });
+    wave_sync();   /* every lane has read the frames at q */
+    state_kinematics<SW::FN, T, Real>(M, SM, lds, lane, q1d, ud);
+    wave_sync();   /* the columns are out, and the joint-local region (LOC / SL) the slot array shares is free */
+    if (lane == 0) lds[SL::BS + LY::TZ] = Real(0);
+    sfor<0, MPL>([&](auto jI) {
+        constexpr int j = decltype(jI)::value;
+        const int s = lane + j * G;
+        Real *bs = lds + SL::BS + s * NSP;
+        L1[j] = 0;
+        if (mi[j] < NM) {
+            const SMuscle<Real> &mu = SM.mus[mi[j]];
+            Real dLs[NSP];
+            muscle_path<SW::PATH, T, Real>(SM, mu, lds, L1[j], dLs);
+            /* so_kernel's structural zeros: a dof that moves every point of the path */
+            unsigned common = ~0u, mov = 0u;
+#pragma unroll
+            for (int p = 0; p < T::MAXPT; ++p) {
+                const DPathPt<Real> &pt = SM.pt[mu.pt_off + (p < mu.npt ? p : 0)];
+                common &= pt.dofmask;
+                mov |= (p < mu.npt && pt.mdof >= 0) ? 1u << pt.mdof : 0u;
+            }
+            const unsigned rigid = common & ~mov;
+#pragma unroll
+            for (int k = 0; k < NSP; ++k) {
+                const int dk = k < mu.nspan ? mu.span[k] : 0;
+                const Real dl = ((rigid >> dk) & 1u) ? Real(0) : dLs[k];
+                bs[k] = k < mu.nspan ? -dl * mu.fiso : Real(0);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < NSP; ++k) bs[k] = Real(0);
+        }
+    });
+    wave_sync();   /* frames, columns, coordinates are dead: [0, U) is the solver's */
+    /* phase 2: the predictor at the two ends of the slot's bracket */
+    const Real h = a.window / Real(a.nsub);
+    Real a0[MPL], l0[MPL], eE[MPL][2], fE[MPL][2], aE[MPL][2], lE[MPL][2];
+    sfor<0, MPL>([&](auto jI) {
+        constexpr int j = decltype(jI)::value;
+        const int s = lane + j * G;
+        a0[j] = 0; l0[j] = 0;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) { eE[j][e] = 0; fE[j][e] = 0; aE[j][e] = 0; lE[j][e] = 0; }
+        if (mi[j] < NM) {
+            const SMuscle<Real> &mu = SM.mus[mi[j]];
+            const size_t row = (size_t)idx * NM + mi[j];
+            a0[j] = GAT(a.act, row, rows);
+            l0[j] = GAT(a.lce, row, rows);
+            const Real one = 1;
+            const Real el = a.emin > mu.amin ? Real(a.emin) : mu.amin;
+            Real eh = a.emax < one ? Real(a.emax) : one;
+            eh = eh < el ? el : eh;   /* an empty bracket collapses onto its lower end */
+            eE[j][0] = el; eE[j][1] = eh;
+#pragma nounroll
+            for (int e = 0; e < 2; ++e) {
+                Real ae, le;
+                const Real f = cmc_predict<T, Real>(SM, mu, a0[j], l0[j], L0[j], L1[j], e ? eh : el, h, a.nsub, ae, le);
+                if (e) { fE[j][1] = f; aE[j][1] = ae; lE[j][1] = le; }
+                else { fE[j][0] = f; aE[j][0] = ae; lE[j][0] = le; }
+            }
+            if (a.force_range) {
+                Real *fr = a.force_range + GIDX(row * 2, rows * 2);
+                fr[0] = fE[j][0]; fr[1] = fE[j][1];
+            }
+            const bool up = fE[j][0] <= fE[j][1];
+            lds[SL::LO + s] = (up ? fE[j][0] : fE[j][1]) / mu.fiso;
+            lds[SL::HI + s] = (up ? fE[j][1] : fE[j][0]) / mu.fiso;
+        }
+    });
+    /* phase 3: the allocation over x = F / F0 */
+    Real lam = 0, tq = 0;
+    if (lane < ND) {
+        lam = a.row_weight ? a.row_weight[lane] : Real(1);
+        tq = GAT(a.tau, (size_t)idx * ND + lane, (size_t)a.n * ND);
+    }
+    Real xv[MPL];
+    const int status = box_qp_solve<T, Real>(SM, lds, lane, mi, lam, tq, xv);
+    if (lane == 0 && a.status) a.status[idx] = status;
+    /* phase 4: the excitation of each slot's force */
+    sfor<0, MPL>([&](auto jI) {
+        constexpr int j = decltype(jI)::value;
+        const int s = lane + j * G;
+        if (mi[j] < NM) {
+            const SMuscle<Real> &mu = SM.mus[mi[j]];
+            const size_t row = (size_t)idx * NM + mi[j];
+            const Real xl = lds[SL::LO + s], xh = lds[SL::HI + s];
+            const bool up = fE[j][0] <= fE[j][1];
+            const bool atlo = !(xv[j] > xl), athi = !atlo && !(xv[j] < xh);
+            /* at a bound (an empty range included): that end of the bracket, its force and its end state */
+            const bool hiend = atlo ? !up : up;
+            Real be = hiend ? eE[j][1] : eE[j][0], bf = hiend ? fE[j][1] : fE[j][0];
+            Real ba = hiend ? aE[j][1] : aE[j][0], bl = hiend ? lE[j][1] : lE[j][0];
+            Real Fs = bf;
+            int rs = 0;
+            if (!atlo && !athi) {
+                Fs = xv[j] * mu.fiso;
+                const Real tolF = a.ftol * mu.fiso;
+                Real ea = eE[j][0], eb = eE[j][1], ga = fE[j][0] - Fs, gb = fE[j][1] - Fs, bg = 0;
+                int ev = 0, side = 0;
+                rs = -1;
+                while (ev < a.max_iter) {
+                    Real ec = eb - gb * (eb - ea) / (gb - ga);
+                    ec = (ec > ea && ec < eb) ? ec : Real(0.5) * (ea + eb);
+                    Real ae, le;
+                    const Real fc = cmc_predict<T, Real>(SM, mu, a0[j], l0[j], L0[j], L1[j], ec, h, a.nsub, ae, le);
+                    const Real gc = fc - Fs, ag = fabs(gc);
+                    ++ev;
+                    if (ev == 1 || ag < bg) { be = ec; bf = fc; ba = ae; bl = le; bg = ag; }
+                    if (ag <= tolF) { rs = ev; break; }
+                    if ((gc < Real(0)) == (gb < Real(0))) {
+                        eb = ec; gb = gc;
+                        ga = side == 1 ? Real(0.5) * ga : ga;
+                        side = 1;
+                    } else {
+                        ea = ec; ga = gc;
+                        gb = side == -1 ? Real(0.5) * gb : gb;
+                        side = -1;
+                    }
+                }
+            }
+            GAT(a.excitation, row, rows) = be;
+            if (a.force) GAT(a.force, row, rows) = Fs;
+            if (a.predicted) GAT(a.predicted, row, rows) = bf;
+            if (a.state_end) {
+                Real *se = a.state_end + GIDX(row * 2, rows * 2);
+                se[0] = ba; se[1] = bl;
+            }
+            if (a.root_status) a.root_status[GIDX(row, rows)] = rs;
+        }
+    });
+    /* tau_muscle = B x, residual = tau - tau_muscle by dof */
+    if (lane < ND && (a.residual || a.tau_muscle)) {
+        Real sum = 0;
+#pragma unroll
+        for (int i = 0; i < T::MAXARM; ++i) {
+            const int src = SM.tau_src[lane][i];
+            const int sx = src / NSP < NM ? src / NSP : NM - 1;
+            sum += lds[SL::BS + src] * lds[SL::X + sx];
+        }
+        if (a.tau_muscle) GAT(a.tau_muscle, (size_t)idx * ND + lane, (size_t)a.n * ND) = sum;
+        if (a.residual) GAT(a.residual, (size_t)idx * ND + lane, (size_t)a.n * ND) = tq - sum;
     }
 }
 
@@ -5221,6 +5515,8 @@ struct Ops {
     void (*ma_launch)(bioim_handle_t *, const MaFields<void> &);
     /* bioim_static_opt's launcher; null for a torque topology and for an fp32 handle (fp64 kernels only) */
     void (*so_launch)(bioim_handle_t *, const SoFields<void> &);
+    /* bioim_cmc's launcher; null as so_launch is */
+    void (*cmc_launch)(bioim_handle_t *, const CmcFields<void> &);
     /* bioim_ik_solve's launcher (every topology); null for an fp32 handle (fp64 kernels only) */
     void (*ik_launch)(bioim_handle_t *, const IkFields<void> &);
     /* bioim_joint_reaction's launcher (every topology, both precisions); < 0: the fp64 image's upload failed */
@@ -5532,6 +5828,10 @@ template <class T> void so_launch_impl(bioim_handle_t *h, const SoFields<void> &
     analysis_launch<BIOIM_EPB>(h, &so_kernel<T, double>, c, lds_bytes<T, double, false>(), h->model, h->smodel);
 }
 
+template <class T> void cmc_launch_impl(bioim_handle_t *h, const CmcFields<void> &c) {
+    analysis_launch<BIOIM_EPB>(h, &cmc_kernel<T, double>, c, lds_bytes<T, double, false>(), h->model, h->smodel);
+}
+
 template <class T> void ik_launch_impl(bioim_handle_t *h, const IkFields<void> &c) {
     analysis_launch<BIOIM_EPB>(h, &ik_kernel<T, double>, c, lds_bytes<T, double, false>(), h->model, h->smodel);
 }
@@ -5602,6 +5902,7 @@ template <class T, typename Real> int upload_smodel(bioim_handle_t *h) {
     ALLOW_LDS((rollout_kernel<T, Real>), (lds_bytes<T, Real, false>()));
     if constexpr (T::NM > 0) ALLOW_LDS((ma_kernel<T, Real>), (lds_bytes<T, Real, false>()));
     if constexpr (T::NM > 0 && std::is_same<Real, double>::value) ALLOW_LDS((so_kernel<T, double>), (lds_bytes<T, double, false>()));
+    if constexpr (T::NM > 0 && std::is_same<Real, double>::value) ALLOW_LDS((cmc_kernel<T, double>), (lds_bytes<T, double, false>()));
     if constexpr (std::is_same<Real, double>::value) ALLOW_LDS((ik_kernel<T, double>), (lds_bytes<T, double, false>()));
     ALLOW_LDS((jr_kernel<T, Real>), (lds_bytes<T, double, false>()));
     if constexpr (std::is_same<Real, double>::value) ALLOW_LDS((ia_kernel<T, double>), (IaLay<T, double>::lds_bytes));
@@ -5623,6 +5924,7 @@ template <class T> bool pick(const bioim_modelpack_t &p, int precision, Ops &ops
     ops.cache_dim = CacheLay<T>::DIM;
     ops.ma_launch = nullptr;
     ops.so_launch = nullptr;
+    ops.cmc_launch = nullptr;
     ops.ik_launch = precision == 64 ? &ik_launch_impl<T> : nullptr;
     ops.ia_launch = precision == 64 ? &ia_launch_impl<T> : nullptr;
     if (precision == 64) ops.jr_launch = &jr_launch_impl<T, double>;
@@ -5633,6 +5935,7 @@ template <class T> bool pick(const bioim_modelpack_t &p, int precision, Ops &ops
         if (precision == 64) ops.ma_launch = &ma_launch_impl<T, double>;
         else ops.ma_launch = &ma_launch_impl<T, float>;
         if (precision == 64) ops.so_launch = &so_launch_impl<T>;
+        if (precision == 64) ops.cmc_launch = &cmc_launch_impl<T>;
     }
     if (precision == 64) {
         ops.launch = &launch_impl<T, double>;
@@ -6407,6 +6710,33 @@ int bioim_static_opt(bioim_handle_t *h, int n, const void *q, const void *u, con
     HIPCHK(hipSetDevice(h->device));
     const SoFields<void> c{n, passive, q, u, tau, row_weight, lo, hi, act, residual, tau_muscle, capacity, status};
     h->ops.so_launch(h, c);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int bioim_cmc(bioim_handle_t *h, int n, const void *q, const void *u, const void *act, const void *lce, const void *q1,
+              const void *tau, const void *row_weight, double T, int nsub, double emin, double emax, double ftol,
+              int max_iter, void *excitation, void *force, void *force_range, void *predicted, void *state_end,
+              void *tau_muscle, void *residual, int32_t *status, int32_t *root_status) {
+    if (!h) return fail(BIOIM_E_ARG, "bioim_cmc: null handle");
+    if (n < 0) return fail(BIOIM_E_ARG, "bioim_cmc: negative n");
+    if (n > 0 && !q) return fail(BIOIM_E_ARG, "bioim_cmc: null q");
+    if (n > 0 && !u) return fail(BIOIM_E_ARG, "bioim_cmc: null u");
+    if (n > 0 && !act) return fail(BIOIM_E_ARG, "bioim_cmc: null act");
+    if (n > 0 && !lce) return fail(BIOIM_E_ARG, "bioim_cmc: null lce");
+    if (n > 0 && !tau) return fail(BIOIM_E_ARG, "bioim_cmc: null tau");
+    if (n > 0 && !excitation) return fail(BIOIM_E_ARG, "bioim_cmc: null excitation");
+    if (!std::isfinite(T) || !std::isfinite(ftol) || !std::isfinite(emin) || !std::isfinite(emax) || !(T > 0) ||
+        !(emin < emax))
+        return fail(BIOIM_E_ARG, "bioim_cmc: T, ftol, emin and emax must be finite with T > 0 and emin < emax");
+    if (nsub < 1 || max_iter < 1) return fail(BIOIM_E_ARG, "bioim_cmc: nsub and max_iter must be at least 1");
+    if (h->nmuscle <= 0) return fail(BIOIM_E_ARG, "bioim_cmc: the model has no muscles");
+    if (h->precision != 64 || !h->ops.cmc_launch) return fail(BIOIM_E_ARG, "bioim_cmc: fp64 handles only");
+    if (n == 0) return 0;
+    HIPCHK(hipSetDevice(h->device));
+    const CmcFields<void> c{n, nsub, max_iter, q, u, act, lce, q1, tau, row_weight, T, emin, emax, ftol,
+                            excitation, force, force_range, predicted, state_end, tau_muscle, residual, status, root_status};
+    h->ops.cmc_launch(h, c);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -273,6 +273,108 @@ int bioim_static_opt(bioim_handle_t *h, int n, const void *q, const void *u, con
                      void *act /* [n][nmuscle], required */, void *residual /* [n][ndof] */,
                      void *tau_muscle /* [n][ndof] */, void *capacity /* [n][nmuscle][2]: Fa, Fp */,
                      int32_t *status /* [n]: iterations used, or -1 cap hit, -2 factorization failed */);
+/* Computed muscle control (OpenSim's CMC, the step after StaticOptimization)
+ * on the handle's model, batched over n arbitrary states — not the handle's
+ * envs: the env state and the realize cache are neither read nor written.
+ * Per state and window [t, t + T]: the excitations e whose muscles, run
+ * through the step's own activation and contraction dynamics (compliant
+ * tendons, the fiber-length state, first-order activation), deliver at t + T
+ * the tendon forces that produce the target generalized force tau (normally
+ * bioim_id_eval's BIOIM_ID_RESIDUAL at the wanted q'').  fp64 handles only.
+ * Inputs, device pointers, dof order as for bioim_id_eval:
+ *   q, u       [n][ndof]     the state at the window's start t;
+ *   act, lce   [n][nmuscle]  the muscle states at t;
+ *   q1         [n][ndof]     the coordinates at t + T; NULL: q + T u (product,
+ *                            then sum, two roundings: the same bits as the
+ *                            caller's own q + T u passed as q1);
+ *   tau        [n][ndof]     the generalized force the muscles are to deliver;
+ *   row_weight [ndof]        lam_d >= 0 as in bioim_static_opt (lam_d = 1 /
+ *                            reserve^2, 0 leaves row d out); NULL: all 1;
+ *   T                        the window length, > 0;
+ *   nsub                     predictor substeps, >= 1 (the step's own count is
+ *                            20 at T = 0.01; the predictor with 5 differs from
+ *                            it by up to 0.28 F0);
+ *   emin, emax               per muscle the bracket is [max(emin, amin_m),
+ *                            min(emax, 1)]; a bracket these leave empty
+ *                            collapses onto its lower end;
+ *   ftol                     root-solve force tolerance in units of F0;
+ *   max_iter                 cap on predictor evaluations per root solve, >= 1.
+ * Four phases per state.
+ *   1. Paths.  L0 is the path length at q; L1 and dL/dq are taken at q1, the
+ *      structural zeros of dL/dq exact as in bioim_static_opt.  Inside the
+ *      window the path length is L(s) = L0 + (s / T)(L1 - L0).
+ *   2. Predictor P_m(e).  From (act_m, lce_m), nsub times the step's muscle
+ *      substep at h = T / nsub with constant excitation e: substep k = 0 ..
+ *      nsub - 1 evaluates the muscle at path length L0 + (k / nsub)(L1 - L0)
+ *      with a cold fiber-velocity start, then a += h da/dt and, unless the
+ *      fiber is clamped, lce += h vce / (1 - h dvce/dlce) cut at l_min (the
+ *      semi-implicit update of the step).  P_m(e) is the tendon force of one
+ *      more evaluation at the end state and L1.  The force range is P_m at the
+ *      two bracket ends; each end keeps its own force, and Fmin_m / Fmax_m are
+ *      the smaller / the larger of the two.
+ *   3. Force allocation over x_m = F_m / F0_m (OpenSim's CMC target, the sum
+ *      of squared muscle stresses):
+ *          minimize sum_m x_m^2 + sum_d lam_d (tau_d - sum_m (-dL_m/dq_d) F0_m x_m)^2
+ *          subject to Fmin_m / F0_m <= x_m <= Fmax_m / F0_m.
+ *      No passive term: F is the whole tendon force.  A muscle with Fmax <=
+ *      Fmin stays bound at Fmin and is never offered to the solver.  The solve
+ *      is bioim_static_opt's active-set iteration (one piece of code: the same
+ *      passes, ties, cap of 8 nmuscle and status codes), started at the lower
+ *      bounds.  F*_m is Fmin_m (Fmax_m) itself where x_m ends on its lower
+ *      (upper) bound, else x_m F0_m.
+ *   4. Root solve per muscle.  F* on a bound: that bound's bracket end (for an
+ *      empty range the lower end), zero evaluations, root_status 0.  Otherwise
+ *      Illinois regula falsi on g(e) = P_m(e) - F*_m:
+ *        a. a, b = the lower, upper bracket end, ga, gb = their forces of
+ *           phase 2 minus F* (opposite signs: F* lies strictly between), no
+ *           side retained;
+ *        b. with max_iter evaluations done: return the evaluated iterate with
+ *           the smallest |g| (the earliest of equals), root_status -1;
+ *        c. c = b - gb (b - a) / (gb - ga), replaced by (a + b) / 2 unless a < c
+ *           < b; gc = P_m(c) - F*, one evaluation;
+ *        d. |gc| <= ftol F0_m: return c, root_status = the evaluations used;
+ *        e. gc and gb of one sign (both < 0 or neither): b, gb = c, gc, and if
+ *           b's side was also the one replaced last, ga = ga / 2; otherwise a,
+ *           ga = c, gc, and if a's side was also the one replaced last, gb =
+ *           gb / 2; back to b.
+ * Outputs (excitation required, the others may be NULL):
+ *   excitation  [n][nmuscle]     the returned excitation e*;
+ *   force       [n][nmuscle]     the allocated force F*;
+ *   force_range [n][nmuscle][2]  P_m at the lower and at the upper bracket
+ *                                end, in that order (phase 3's bounds are
+ *                                their min and max);
+ *   predicted   [n][nmuscle]     P_m(e*);
+ *   state_end   [n][nmuscle][2]  the predicted activation and fiber length at
+ *                                t + T under e* (bioim_muscle_eval at q1 with
+ *                                them returns predicted as its tendon force);
+ *   tau_muscle  [n][ndof]        sum_m (-dL_m/dq_d) F0_m x_m;
+ *   residual    [n][ndof]        tau - tau_muscle, on every dof;
+ *   status      [n] int32        phase 3: the solver's passes (>= 0), -1: its
+ *                                cap was hit, -2: a factorization failed or a
+ *                                NaN came in;
+ *   root_status [n][nmuscle] int32  phase 4: evaluations used; 0 for a muscle
+ *                                on a bound or with an empty range; -1: the cap.
+ * Every loop is bounded: nsub + 1 muscle evaluations per predictor, 2 +
+ * max_iter predictors per muscle, 8 nmuscle solver passes, and the
+ * fiber-velocity iteration's own cap.  A state's result does not depend on n
+ * or on the other states, and a repeated call repeats it bit for bit.
+ * Out of scope: residual actuators on the pelvis (bioim_set_external_forces
+ * is the place to apply them), inverting the envs' action smoothing, the
+ * torque models, fp32 (the allocation has bioim_static_opt's conditioning)
+ * and RRA.  BIOIM_E_ARG, before any device call and in this order, for: a
+ * null handle, n < 0, with n > 0 a null q, u, act, lce, tau or excitation (in
+ * that order), T, ftol, emin or emax not finite or T <= 0 or emin >= emax,
+ * nsub < 1 or max_iter < 1, a model without muscles, an fp32 handle.  n == 0
+ * returns BIOIM_OK without a launch.  Asynchronous on the handle's stream;
+ * synchronizes nothing.  No reference counterpart (the reference drives its
+ * muscles from a policy; it ships no controller). */
+int bioim_cmc(bioim_handle_t *h, int n, const void *q, const void *u, const void *act, const void *lce,
+              const void *q1 /* [n][ndof], NULL = q + T u */, const void *tau,
+              const void *row_weight /* device [ndof], NULL = all 1 */, double T, int nsub, double emin, double emax,
+              double ftol, int max_iter, void *excitation /* [n][nmuscle], required */, void *force /* [n][nmuscle] */,
+              void *force_range /* [n][nmuscle][2] */, void *predicted /* [n][nmuscle] */,
+              void *state_end /* [n][nmuscle][2]: activation, fiber length */, void *tau_muscle /* [n][ndof] */,
+              void *residual /* [n][ndof] */, int32_t *status /* [n] */, int32_t *root_status /* [n][nmuscle] */);
 /* Marker inverse kinematics (OpenSim's InverseKinematicsTool, the first link
  * of the chain IK -> InverseDynamics -> StaticOptimization) on the handle's
  * model, batched over n frames — not the handle's envs: the env state and the

@@ -59,7 +59,7 @@ def kernels(lines: list[str]):
 
 
 RISKY = ('masked-use+addr', 'undefined', 'undefined+addr')
-KERNELS = ('env_kernel', 'id_kernel', 'rollout_kernel', 'ma_kernel', 'so_kernel', 'ik_kernel', 'jr_kernel', 'ia_kernel', 'bk_kernel')   # the kernel templates of the per-topology and fused units
+KERNELS = ('env_kernel', 'id_kernel', 'rollout_kernel', 'ma_kernel', 'so_kernel', 'cmc_kernel', 'ik_kernel', 'jr_kernel', 'ia_kernel', 'bk_kernel')   # the kernel templates of the per-topology and fused units
 
 
 def _scan_unit(obj):
